@@ -7,15 +7,26 @@ GatedCRF on synthetic 256x256 4-class scribble slices, batch 64 per GPU, data-pa
         bench.py --gpus N --steps K --warmup W
 
 One "step" = masks -> forward -> loss head (+GatedCRF) -> backward -> gradient all-reduce -> SGD, i.e. one optimiser
-step on one batch of 64 slices per GPU, inputs resident in HBM.  Prints ONE JSON line on rank 0 with the `roofline`
-(HIP events around every launch of the dominant kernel family, recorded on the launch stream) and, at N=1, the
-`cpu_baseline` (the oracle's torch-CPU restatement of the same step, timed on this box's host cores).
+step on one batch of 64 slices per GPU, inputs resident in HBM.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times exactly --steps steps in one region, writes the last step's outputs if
+--dump-outputs DIR is given, and prints the line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`).
+Everything else moves behind --full: three timed regions by default (--repeats), the `roofline` (HIP events around
+every launch of the dominant kernel family, recorded on the launch stream; rocprofv3 counter passes for its traffic),
+the nested split-precision record, the drop-in module path's record and, at N=1, the `cpu_baseline` (the oracle's
+torch-CPU restatement of the same step, timed on this box's host cores).
+
+--dump-outputs DIR writes, right after the timed steps, what the timed path hands its caller after its last step:
+the flat parameter arena (`params.npy`), the gradient of that step (`grads.npy`), the SGD momentum (`momentum.npy`),
+the BatchNorm running statistics (`buffers.npy`), the EMA teacher's parameters where there is one (`teacher_params.npy`)
+and every loss term (`loss_<name>.npy`), float32 / float64.  Inputs, initial weights, dropout masks and the beta stream
+are seeded, so the same arguments give the same inputs in every run.
 
 unet_cct runs its two decoders on two streams (+5 % step rate; mean teacher: the teacher's forward), so in the timed region launches of the dominant kernel
 overlap each other and a per-launch duration no longer measures the kernel.  The `roofline` object is therefore taken
 from a short second segment of the same workload in the same process with the decoders serialised
 (`wsl_net_concurrent(0)`), where launches do not overlap; the timed region's own (overlapping) per-launch figures
-are reported next to it as `roofline.timed_region_overlapped`.  `--serial-decoders` serialises the timed region too.
+are reported next to it as `roofline.timed_region_overlapped` (--full).  `--serial-decoders` serialises the timed region too.
 """
 import argparse
 import ctypes as C
@@ -47,11 +58,18 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)      # >= 50 timed steps after >= 10 warm-up steps
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="the full record: besides the headline also the roofline / per-kernel figures, the split-precision record, the "
+                         "module path, the CPU baseline (each still switchable off with its --no-* option) and --repeats 3 by default.  "
+                         "Without it the run only times --steps steps once and prints the headline fields")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32 / "
+                         "float64): params, grads, momentum, buffers, teacher_params (EMA teacher only), loss_<term>")
     ap.add_argument("--conv-precision", default="f32", choices=["f32", "split_f16x3"],
                     help="f32 (the headline) | split_f16x3: the split-precision conv path (f16 hi / lo operands, three MFMA "
                          "passes, fp32 accumulate) as the primary record (dtype f32-split-f16x3)")
     ap.add_argument("--no-split-record", action="store_true",
-                    help="by default an f32 run is followed by the SAME workload on the split-precision conv path (own engine, own "
+                    help="with --full an f32 run is followed by the SAME workload on the split-precision conv path (own engine, own "
                          "warm-up, >= 20 timed steps, own serialised roofline segment), nested as \"split_f16x3\" in the one JSON line")
     ap.add_argument("--lib", default=None, help="A/B timing only: another hipcc build of libwslhip.so (e.g. tools/exp/libwslhip_prev.so) instead "
                     "of the in-tree product library; the line says so in config.library")
@@ -64,7 +82,7 @@ def parse():
     ap.add_argument("--no-prof", action="store_true")
     ap.add_argument("--no-pmc-refresh", action="store_true", help="do not collect roofline.traffic in this run (then the newest committed "
                     "profiles/r*_pmc_traffic.json record is quoted, marked as such)")
-    ap.add_argument("--pmc-refresh", action="store_true", help="(the default since round 5 when N=1) collect roofline.traffic IN THIS RUN -- two "
+    ap.add_argument("--pmc-refresh", action="store_true", help="(the --full default when N=1) collect roofline.traffic IN THIS RUN -- two "
                     "rocprofv3 counter passes (FETCH_SIZE, WRITE_SIZE; counters only, no trace domain) of this same command at "
                     "--steps 2 --warmup 1, aggregated by tools/pmc_traffic.py (adds about a minute)")
     ap.add_argument("--prof-timed", action="store_true",
@@ -82,10 +100,11 @@ def parse():
                     help="engine (default, the headline): the fused TrainEngine.  modules: the DROP-IN module path INTEGRATION.md section 2 hands a "
                          "maintainer -- net_factory() + torch.softmax + PartialCrossEntropyLoss + ModelLossSemsegGatedCRF + loss.backward() + "
                          "torch.optim.SGD, the loop of train_weakly_supervised_pCE_GatedCRFLoss_2D.py:108-130 -- same batch and size; prints its own "
-                         "JSON line.  A default N=1 run nests that line as \"modules_path\" (VERDICT r5 item 5)")
-    ap.add_argument("--no-modules-record", action="store_true", help="do not run / nest the --path modules record in the default line")
-    ap.add_argument("--repeats", type=int, default=3, help="timed regions of --steps steps each (same engine, barrier + synchronize around each); "
-                    "`value` / `ms_per_step` are the MEDIAN region's, min / max / all travel in `repeats` (VERDICT r5 item 4b)")
+                         "JSON line.  An N=1 --full run nests that line as \"modules_path\" (VERDICT r5 item 5)")
+    ap.add_argument("--no-modules-record", action="store_true", help="do not run / nest the --path modules record in the --full line")
+    ap.add_argument("--repeats", type=int, default=None, help="timed regions of --steps steps each (same engine, barrier + synchronize around each); "
+                    "`value` / `ms_per_step` are the MEDIAN region's, min / max / all travel in `repeats` (VERDICT r5 item 4b).  "
+                    "Default 3 with --full, else 1")
     ap.add_argument("--selftest-emulator", action="store_true",
                     help="TEST HARNESS ONLY (tests/test_dp.py), never a measurement: the launch / rendezvous / timing / reporting logic of this "
                          "script on the CPU -- ranks over gloo, the kernel sources in the test-only host emulator (tests/emul), value = null")
@@ -222,6 +241,52 @@ def median_region(times):
     return times[i], i
 
 
+def one_step_kernel_count(step):
+    """device kernels of ONE extra step by name: the library's (wsl::) against ATen's / the runtime's -> (aten, wsl, largest non-library)"""
+    aten = wslk = None
+    top = []
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            step()
+            torch.cuda.synchronize()
+        names = [e.name for e in prof.events() if getattr(e, "device_type", None) is not None and "CUDA" in str(e.device_type).upper()]
+        wslk = sum(1 for n in names if "wsl::" in n)
+        aten = len(names) - wslk
+        cnt = {}
+        for e in prof.events():
+            if getattr(e, "device_type", None) is not None and "CUDA" in str(e.device_type).upper() and "wsl::" not in e.name:
+                c = cnt.setdefault(e.name[:80], [0, 0.0])
+                c[0] += 1
+                c[1] += float(getattr(e, "device_time", 0.0) or getattr(e, "cuda_time", 0.0) or 0.0)
+        top = [{"kernel": k, "launches": v[0], "us": round(v[1], 1)} for k, v in sorted(cnt.items(), key=lambda kv: -kv[1][1])[:8]]
+    except Exception as e:                                 # noqa: BLE001  (the count is a diagnosis, never the measurement)
+        top = [{"profiler_failed": repr(e)[:200]}]
+    return aten, wslk, top
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, arrays, losses):
+    """DIR/<name>.npy for every device array (float32) and every loss term (float64 scalar).  An array that would take the
+    dump past 64 MB in all is replaced by a fixed, seeded sample of its elements (never the case for the networks here)"""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    host = {k: v.detach().reshape(-1).to(torch.float32).cpu().numpy() for k, v in arrays.items() if v is not None}
+    budget = DUMP_LIMIT_BYTES - 4096 * (len(host) + len(losses))
+    total = sum(a.nbytes for a in host.values())
+    for k in sorted(host):
+        a = host[k]
+        if total > budget:
+            keep = max(1, a.size * budget // total)
+            idx = np.sort(np.random.default_rng(2022).choice(a.size, size=keep, replace=False))
+            a = a[idx]
+        np.save(os.path.join(outdir, f"{k}.npy"), a)
+    for k, v in losses.items():
+        np.save(os.path.join(outdir, f"loss_{k}.npy"), np.float64(v))
+
+
 def modules_path(args):
     """The drop-in MODULE path: what a maintainer gets by swapping the reference trainer's three imports and
     keeping its loop -- ref: train_weakly_supervised_pCE_GatedCRFLoss_2D.py:108-130 (`unet`), and for `unet_cct` the dual-branch form of
@@ -284,26 +349,10 @@ def modules_path(args):
         times.append(time.perf_counter() - t0)
     dt, _ = median_region(times)
     rates = [args.batch * args.steps / t for t in times]
-    # device kernels of ONE step by name: the library's (wsl::) against ATen's / the runtime's
-    aten = wslk = None
-    top = []
-    try:
-        from torch.profiler import ProfilerActivity, profile
-        with profile(activities=[ProfilerActivity.CUDA]) as prof:
-            step()
-            torch.cuda.synchronize()
-        names = [e.name for e in prof.events() if getattr(e, "device_type", None) is not None and "CUDA" in str(e.device_type).upper()]
-        wslk = sum(1 for n in names if "wsl::" in n)
-        aten = len(names) - wslk
-        cnt = {}
-        for e in prof.events():
-            if getattr(e, "device_type", None) is not None and "CUDA" in str(e.device_type).upper() and "wsl::" not in e.name:
-                c = cnt.setdefault(e.name[:80], [0, 0.0])
-                c[0] += 1
-                c[1] += float(getattr(e, "device_time", 0.0) or getattr(e, "cuda_time", 0.0) or 0.0)
-        top = [{"kernel": k, "launches": v[0], "us": round(v[1], 1)} for k, v in sorted(cnt.items(), key=lambda kv: -kv[1][1])[:8]]
-    except Exception as e:                                 # noqa: BLE001  (the count is a diagnosis, never the measurement)
-        top = [{"profiler_failed": repr(e)[:200]}]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"params": model.flat_params(), "grads": model.flat_grads(), "buffers": model._buf_arena},
+                     {k: float(v) for k, v in last.items()})
+    aten, wslk, top = one_step_kernel_count(step) if args.full else (None, None, [])
     return {"path": "modules", "value": round(args.batch * args.steps / dt, 2), "unit": "slices/s", "ms_per_step": round(1e3 * dt / args.steps, 3),
             "steps": args.steps, "warmup": args.warmup,
             "repeats": {"n": len(times), "values": [round(r, 2) for r in rates], "min": round(min(rates), 2), "max": round(max(rates), 2)},
@@ -320,7 +369,7 @@ def modules_path_subprocess(args):
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--path", "modules", "--loss", args.loss, "--net", args.net, "--size", str(args.size),
            "--batch", str(args.batch), "--crf-radius", str(args.crf_radius), "--steps", str(max(10, min(args.steps, 20))),
-           "--warmup", str(max(3, min(args.warmup, 5))), "--repeats", "3", "--conv-precision", args.conv_precision]
+           "--warmup", str(max(3, min(args.warmup, 5))), "--repeats", "3", "--conv-precision", args.conv_precision, "--full"]
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=240)
         for line in reversed(r.stdout.strip().splitlines()):
@@ -333,6 +382,13 @@ def modules_path_subprocess(args):
 
 def main():
     args = parse()
+    if args.repeats is None:
+        args.repeats = 3 if args.full else 1
+    if not args.full:
+        # a plain run: the headline's one timed region and nothing else (no events, no second segments, no child runs)
+        args.no_prof = args.no_split_record = args.no_cpu_baseline = args.no_modules_record = args.no_pmc_refresh = True
+        if args.pmc_refresh or args.prof_timed:
+            raise SystemExit("--pmc-refresh / --prof-timed are part of the --full record: add --full")
     if args.loss in ("mean_teacher", "ustm", "pce_tv", "pce_ms", "pce_entropy", "ce_dice"):
         args.net = "unet"                                  # config 4 (and USTM): single-decoder student + EMA teacher
         if args.loss != "mean_teacher":
@@ -459,6 +515,11 @@ def main():
     n_rep = 1 if emu else max(1, args.repeats)
     eng, dt, dt_own, region_s = timed_region(args.conv_precision, args.steps, args.warmup, n_rep)
     losses = eng.losses()
+    if args.dump_outputs and rank == 0:        # before anything below runs more steps on this engine
+        m_ = eng.model
+        dump_outputs(args.dump_outputs, {"params": m_.flat_params(), "grads": m_.flat_grads(), "momentum": eng.mom[:eng.n],
+                                         "buffers": m_._buf_arena, "teacher_params": eng.teacher.flat_params() if eng.teacher else None},
+                     losses)
     dp_diag = None
     if eng.dp:
         # self-diagnosing N > 1 line: what each rank saw, how long the main stream sat waiting for the
@@ -515,7 +576,7 @@ def main():
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import pmc_traffic as agg
         tmp = tempfile.mkdtemp(prefix="wsl_pmc_", dir="/tmp")
-        child = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-prof", "--no-split-record", "--no-pmc-refresh",
+        child = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--repeats", "3", "--no-cpu-baseline", "--no-prof", "--no-split-record", "--no-pmc-refresh",
                  "--serial-decoders", "--conv-precision", args.conv_precision, "--loss", args.loss, "--net", args.net, "--batch", str(args.batch),
                  "--size", str(args.size), "--crf-radius", str(args.crf_radius)]
         try:

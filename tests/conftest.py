@@ -16,8 +16,26 @@ def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
 
 
+class _Fixture(dict):
+    """the arrays of a fixture stored in parts, as one mapping with NpzFile's `files`"""
+
+    @property
+    def files(self):
+        return list(self)
+
+
 def golden(name):
-    return np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False)
+    """name.npz; a fixture that tests/golden/make_golden.py::save() split to keep every file under 1 MiB also has
+    name.part2.npz, ... (disjoint keys), read back as one mapping"""
+    g = np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False)
+    parts = sorted(f for f in os.listdir(GOLDEN) if f.startswith(name + ".part") and f.endswith(".npz"))
+    if not parts:
+        return g
+    out = _Fixture((k, g[k]) for k in g.files)
+    for f in parts:
+        with np.load(os.path.join(GOLDEN, f), allow_pickle=False) as p:
+            out.update((k, p[k]) for k in p.files)
+    return out
 
 
 def rel_err(a, b, floor=1e-6):

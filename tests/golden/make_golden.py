@@ -21,9 +21,11 @@ replaced (here only) by recording equivalents so the fixture can carry the exact
 Bernoulli masks the reference forward used.
 """
 import ast
+import glob
 import os
 import random
 import sys
+import zipfile
 
 import numpy as np
 import torch
@@ -135,10 +137,37 @@ def load_det(module, seed):
     return vals
 
 
+PART_LIMIT = 1000 * 1024      # a committed file stays under 1 MiB
+
+
 def save(name, **arrs):
+    """name.npz; a fixture that compresses to more than PART_LIMIT is split by case tag (the key prefix before the first '_') over
+    name.npz, name.part2.npz, ... (first fit, tags in key order); tests/conftest.py::golden() reads the parts back as one mapping"""
+    for old in glob.glob(os.path.join(HERE, name + ".part*.npz")):
+        os.remove(old)
     path = os.path.join(HERE, name + ".npz")
     np.savez_compressed(path, **arrs)
-    print(f"  {name}.npz  {os.path.getsize(path)/1024:.1f} KiB")
+    if os.path.getsize(path) > PART_LIMIT:
+        size = {}
+        with zipfile.ZipFile(path) as z:
+            for i in z.infolist():
+                tag = i.filename.split("_")[0]
+                size[tag] = size.get(tag, 0) + i.compress_size + 2 * len(i.filename) + 128
+        parts = []
+        for tag in dict.fromkeys(k.split("_")[0] for k in arrs):
+            for p in parts:
+                if p[0] + size[tag] <= PART_LIMIT:
+                    p[0] += size[tag]
+                    p[1].append(tag)
+                    break
+            else:
+                parts.append([size[tag], [tag]])
+        for n, (_, tags) in enumerate(parts):
+            np.savez_compressed(path if n == 0 else os.path.join(HERE, f"{name}.part{n + 1}.npz"),
+                                **{k: v for k, v in arrs.items() if k.split("_")[0] in tags})
+    for p in [path] + sorted(glob.glob(os.path.join(HERE, name + ".part*.npz"))):
+        print(f"  {os.path.basename(p)}  {os.path.getsize(p)/1024:.1f} KiB")
+        assert os.path.getsize(p) < 1 << 20, p
 
 
 def grads_of(module):

@@ -229,3 +229,25 @@ def test_bench_rank_failure_takes_the_job_down():
     assert not docs
     assert "injected failure of rank 1" in r.stderr
     assert time.time() - t0 < 300
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_step(tmp_path):
+    """A plain run times exactly --steps steps in one region and reports ms_per_step without the --full extras; --dump-outputs DIR
+    writes the last timed step's results as DIR/<name>.npy (float32 / float64, <= 64 MB), identical in two runs with the same arguments"""
+    dumps = []
+    for run in ("a", "b"):
+        d = str(tmp_path / run)
+        r, docs = _bench_selftest(1, extra=["--dump-outputs", d], steps=1)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        assert len(docs) == 1, r.stdout
+        line = docs[0]
+        assert line["steps"] == 1 and line["repeats"]["n"] == 1 and line["ms_per_step"] > 0
+        assert line["roofline"] is None and "split_f16x3" not in line and "cpu_baseline" not in line and "modules_path" not in line
+        dumps.append({f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))})
+    a, b = dumps
+    assert sorted(a) == ["buffers", "grads", "loss_ce", "loss_loss", "loss_n_valid", "loss_pse", "momentum", "params"], sorted(a)
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert np.isfinite(a["loss_loss"]) and np.abs(a["grads"]).max() > 0
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k

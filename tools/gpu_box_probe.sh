@@ -3,7 +3,7 @@
 # sampled by rocm-smi during the two-stream run, host facts
 set -u
 O="$1"; R="${GRAFT_REPO_ROOT:-$(pwd)}"; mkdir -p "$R/$O"; cd "$R"
-B="python bench.py --no-cpu-baseline --no-split-record --no-pmc-refresh --no-prof --steps 40 --warmup 10"
+B="python bench.py --full --no-cpu-baseline --no-split-record --no-pmc-refresh --no-prof --steps 40 --warmup 10"
 ( for i in $(seq 1 40); do rocm-smi --showclocks --showpower --showtemp --json 2>/dev/null | head -c 1500; echo; sleep 0.5; done ) > "$O/smi.log" 2>&1 &
 SMI=$!
 $B 2>/dev/null | tail -1 > "$O/bench_two.json"

@@ -3,7 +3,7 @@
 O="$1"; R="${GRAFT_REPO_ROOT:-$(pwd)}"; mkdir -p "$R/$O"; cd "$R"
 (timeout 1200 python -m pytest tests -m gpu -q --tb=short 2>&1 | tail -5) > "$O/pytest_gpu.log"
 (timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1) > "$O/smoke.log"
-(timeout 600 python bench.py 2>"$O/bench_stderr.log" | tail -1) > "$O/bench_default.json"
+(timeout 600 python bench.py --full 2>"$O/bench_stderr.log" | tail -1) > "$O/bench_default.json"
 cat "$O/pytest_gpu.log" "$O/smoke.log"; python - "$O/bench_default.json" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read()); r = d["roofline"]

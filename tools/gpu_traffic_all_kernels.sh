@@ -1,7 +1,7 @@
 #!/usr/bin/env bash
 # HBM traffic of EVERY kernel of the f32 step (FETCH_SIZE / WRITE_SIZE, separate passes, decoders serialised), per kernel name
 O="$1"; R="${GRAFT_REPO_ROOT:-$(pwd)}"; mkdir -p "$R/$O"; cd /tmp; export TMPDIR=/tmp
-B="python $R/bench.py --no-cpu-baseline --no-split-record --steps 2 --warmup 1 --serial-decoders --no-prof"
+B="python $R/bench.py --full --no-cpu-baseline --no-split-record --steps 2 --warmup 1 --serial-decoders --no-prof"
 for c in FETCH_SIZE WRITE_SIZE "TCC_HIT_sum TCC_MISS_sum"; do
   d=$(echo $c | cut -d' ' -f1)
   timeout 300 rocprofv3 --pmc $c --output-format csv -d "$R/$O/pmc_$d" -- $B > /dev/null 2>&1
