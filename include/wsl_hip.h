@@ -437,6 +437,50 @@ int wsl_net_backward(const WslNetDesc* d, const float* params, const float* x, c
                      const float* const* cmasks, const float* dlogits_main, const float* dlogits_aux, float* grads,
                      void* ws, size_t ws_bytes, int phase, void* stream);
 
+/* ------------------------------------------------------------------------------------------------ dilated 3x3 convolutions
+ * nn.Conv2d(Ci, Co, 3, padding=dil, dilation=dil) of PNet2D (ref: networks/pnet.py PNetBlock): output size = input size.  The same
+ * loader / epilogue contract as wsl_conv2d_fwd (WslSrc a [+ b], batch strides, bias, BatchNorm (sum, M2) partials [Co][nblk][2] with
+ * nblk = wsl_conv2d_dil_stat_blocks() for wsl_bn_stats_finalize); ks must be 3, dil >= 1.  wmode 0: w is [Co][Ci][3][3] (forward);
+ * wmode 1: data gradient, w is the FORWARD weight [Ci][Co][3][3] used flipped (a dilation-dil conv again).  Row-phase tiles: any H, W
+ * and dilation >= 1 are computed (for dil > the tile width the three column taps are staged as separate windows, so the tile's LDS
+ * stays bounded). */
+int wsl_conv2d_dil_fwd(const WslSrc* a, const WslSrc* b, const float* w, const float* bias, float* y, int64_t y_bs, int N, int H,
+                       int W, int Co, int ks, int dil, int wmode, float* stat_part, float* stat_cnt, void* stream);
+int wsl_conv2d_dil_stat_blocks(int N, int H, int W, int Ci, int Co, int dil);
+/* dw[Co][Ci][3][3] = sum dy[n,co,y,x] * in[n,ci,y+dil(ky-1),x+dil(kx-1)], db[Co] = sum dy (db may be NULL): partials in ws, reduced by
+ * wsl_wgrad_reduce_batch (the _partial form leaves that to the caller, as wsl_conv2d_wgrad_partial). */
+int wsl_conv2d_dil_wgrad(const WslSrc* a, const WslSrc* b, const float* dy, int64_t dy_bs, float* dw, float* db, int N, int H, int W,
+                         int Co, int ks, int dil, void* ws, size_t ws_bytes, void* stream);
+size_t wsl_conv2d_dil_wgrad_ws_bytes(int N, int H, int W, int Ci, int Co, int ks, int dil);
+int wsl_conv2d_dil_wgrad_partial(const WslSrc* a, const WslSrc* b, const float* dy, int64_t dy_bs, float* dw, float* db, int N, int H,
+                                 int W, int Co, int ks, int dil, void* ws, size_t ws_bytes, WslWgradPending* pending, void* stream);
+
+/* ------------------------------------------------------------------------------------------------ PNet2D
+ * PNet2D(in_chns, n_class, num_filters F, ratios) (ref: networks/pnet.py; factory: net_factory.py -> F 64, ratios [1,2,4,8,16]):
+ * five blocks conv3x3(dil r_k) -> BN -> LeakyReLU -> conv3x3(dil r_k) -> BN -> LeakyReLU, cat of the five block outputs (5F),
+ * catblock 1x1 5F->5F -> LeakyReLU -> 1x1 5F->2F -> LeakyReLU, out: Dropout2d(0.3) -> 1x1 2F->F -> LeakyReLU -> Dropout2d(0.3) -> 1x1
+ * F->n_class.  Arenas and entries as the UNet's (WslNetEntry; parameters() order = registration order: conv1, conv2, in1, in2 of each
+ * block, then catblock, then out).  fp32 only. */
+typedef struct WslPNetDesc {
+  int32_t in_chns, n_class, num_filters;
+  int32_t ratios[5];
+  int32_t N, H, W;     /* any H, W */
+} WslPNetDesc;
+int wsl_pnet_num_entries(const WslPNetDesc* d);
+int wsl_pnet_entry(const WslPNetDesc* d, int i, WslNetEntry* out);
+int64_t wsl_pnet_param_count(const WslPNetDesc* d);         /* 486,596 for the factory config at (1, 4) */
+int64_t wsl_pnet_block_param_count(const WslPNetDesc* d);   /* the five blocks (the head of the arena) */
+int64_t wsl_pnet_buffer_count(const WslPNetDesc* d);
+size_t wsl_pnet_ws_bytes(const WslPNetDesc* d);
+/* cmasks[2]: the Dropout2d multipliers [N,2F] (before out.conv1) and [N,F] (before out.conv2), 0 or 1/(1-p); NULL entries (or
+ * training == 0) = identity.  Keeps what the backward needs in ws. */
+int wsl_pnet_forward(const WslPNetDesc* d, const float* params, float* buffers, int64_t* nbt, const float* x,
+                     const float* const* cmasks, int training, float* logits, void* ws, size_t ws_bytes, void* stream);
+/* Backward of the last training forward held in ws; grads as wsl_net_backward.  phase: 0 = all, 1 = catblock + out (final when it
+ * returns), 2 = the blocks (after 1). */
+int wsl_pnet_backward(const WslPNetDesc* d, const float* params, const float* x, const float* const* cmasks, const float* dlogits,
+                      float* grads, void* ws, size_t ws_bytes, int phase, void* stream);
+
 /* ------------------------------------------------------------------------------------------------ transposed-conv UpBlock
  * (opt-in: ref networks/unet.py:47-68 with bilinear=False -- a branch the reference's Decoder never selects.)
  * nn.ConvTranspose2d(Ci, Co, kernel_size=2, stride=2): out[n][co][2i+a][2j+b] = bias[co] + sum_ci x[n][ci][i][j] w[ci][co][a][b],

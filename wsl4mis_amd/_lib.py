@@ -45,6 +45,11 @@ class WslUpBlockDesc(C.Structure):
                 ("dropout_p", C.c_float)]
 
 
+class WslPNetDesc(C.Structure):
+    _fields_ = [("in_chns", C.c_int32), ("n_class", C.c_int32), ("num_filters", C.c_int32), ("ratios", C.c_int32 * 5),
+                ("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32)]
+
+
 class WslNetEntry(C.Structure):
     _fields_ = [("name", C.c_char * 96), ("kind", C.c_int32), ("ndim", C.c_int32), ("shape", C.c_int64 * 4),
                 ("offset", C.c_int64)]
@@ -59,6 +64,7 @@ class WslAugSample(C.Structure):
 i32, i64, f32, f64, sz = C.c_int, C.c_int64, C.c_float, C.c_double, C.c_size_t
 PS, PD, PE = C.POINTER(WslSrc), C.POINTER(WslNetDesc), C.POINTER(WslNetEntry)
 PP = C.POINTER(c_fp)
+PQ = C.POINTER(WslPNetDesc)
 
 _PROTOS = {
     "wsl_version": (i32, []),
@@ -155,6 +161,20 @@ _PROTOS = {
     "wsl_upblock_t_ws_bytes": (sz, [C.POINTER(WslUpBlockDesc)]),
     "wsl_upblock_t_forward": (i32, [C.POINTER(WslUpBlockDesc), c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, i32, c_fp, c_fp, sz, c_fp]),
     "wsl_upblock_t_backward": (i32, [C.POINTER(WslUpBlockDesc), c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, sz, c_fp]),
+    "wsl_conv2d_dil_fwd": (i32, [PS, PS, c_fp, c_fp, c_fp, i64, i32, i32, i32, i32, i32, i32, i32, c_fp, c_fp, c_fp]),
+    "wsl_conv2d_dil_stat_blocks": (i32, [i32, i32, i32, i32, i32, i32]),
+    "wsl_conv2d_dil_wgrad": (i32, [PS, PS, c_fp, i64, c_fp, c_fp, i32, i32, i32, i32, i32, i32, c_fp, sz, c_fp]),
+    "wsl_conv2d_dil_wgrad_ws_bytes": (sz, [i32, i32, i32, i32, i32, i32, i32]),
+    "wsl_conv2d_dil_wgrad_partial": (i32, [PS, PS, c_fp, i64, c_fp, c_fp, i32, i32, i32, i32, i32, i32, c_fp, sz,
+                                           C.POINTER(WslWgradPending), c_fp]),
+    "wsl_pnet_num_entries": (i32, [PQ]),
+    "wsl_pnet_entry": (i32, [PQ, i32, PE]),
+    "wsl_pnet_param_count": (i64, [PQ]),
+    "wsl_pnet_block_param_count": (i64, [PQ]),
+    "wsl_pnet_buffer_count": (i64, [PQ]),
+    "wsl_pnet_ws_bytes": (sz, [PQ]),
+    "wsl_pnet_forward": (i32, [PQ, c_fp, c_fp, c_fp, c_fp, PP, i32, c_fp, c_fp, sz, c_fp]),
+    "wsl_pnet_backward": (i32, [PQ, c_fp, c_fp, PP, c_fp, c_fp, c_fp, sz, i32, c_fp]),
     "wsl_net_num_entries": (i32, [PD]),
     "wsl_net_entry": (i32, [PD, i32, PE]),
     "wsl_net_param_count": (i64, [PD]),
