@@ -252,6 +252,30 @@ def softmax_mse(a, b):
     return (F.softmax(a, 1) - F.softmax(b, 1)) ** 2
 
 
+def entropy_loss(p, C):
+    """losses.entropy_loss(p, C) (losses.py:30-36): mean over pixels of -sum_c p log(p + 1e-6), divided by log(C); p [N,C,...] is
+    already a softmax and C only the normaliser."""
+    ent = -torch.sum(p * torch.log(p + 1e-6), dim=1) / math.log(C)
+    return torch.mean(ent)
+
+
+def ustm_consistency(a, b, pmean, threshold):
+    """The consistency term of train_weakly_supervised_ustm_2D.py:141-152 on logits a (student, differentiated) and b (teacher):
+    mask = [-sum_c pmean log(pmean + 1e-6) < threshold]; sum(mask * (softmax(a) - softmax(b))^2) / (2 sum(mask) + 1e-16).
+    Returns (loss, sum(mask))."""
+    unc = -1.0 * torch.sum(pmean * torch.log(pmean + 1e-6), dim=1, keepdim=True)
+    mask = (unc < threshold).to(a.dtype)
+    dist = softmax_mse(a, b.detach())
+    return torch.sum(mask * dist) / (2 * torch.sum(mask) + 1e-16), torch.sum(mask)
+
+
+def mixprob(z1, z2, beta):
+    """The prediction the GatedCRF term regularises: beta * softmax(z1) + (1 - beta) * softmax(z2) (train_ACDC_scribblevc.py:171-206);
+    z2 None: softmax(z1) (pCE_GatedCRFLoss_2D.py:112)."""
+    s1 = torch.softmax(z1, 1)
+    return s1 if z2 is None else beta * s1 + (1.0 - beta) * torch.softmax(z2, 1)
+
+
 def ours_proposed_loss(o1, o2, label_u8, beta):
     """ours_proposed.py:110-125."""
     s1, s2 = torch.softmax(o1, 1), torch.softmax(o2, 1)

@@ -845,8 +845,10 @@ static int bnact_bwd_finish_impl(const float* g, int64_t g_bs, const float* y, c
                                  int channel_major, void* ws, size_t ws_bytes, uint32_t* dy_amax, int g_is_d, void* stream) {
   WSL_REQUIRE(g && y && mean && invstd && gamma && beta && dy && ws && part, "bnact_bwd_finish: null argument");
   WSL_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0 && nblk > 0, "bnact_bwd_finish: bad shape");
-  WSL_REQUIRE(ws_bytes >= wsl_bnact_bwd_finish_ws_bytes(N, C, H, W, dy_amax != nullptr),
-              "bnact_bwd_finish: workspace too small (wsl_bnact_bwd_finish_ws_bytes)");
+  if (ws_bytes < wsl_bnact_bwd_finish_ws_bytes(N, C, H, W, dy_amax != nullptr)) {
+    set_error("bnact_bwd_finish: workspace %zu < %zu", ws_bytes, wsl_bnact_bwd_finish_ws_bytes(N, C, H, W, dy_amax != nullptr));
+    return WSL_EWORKSPACE;
+  }
   BnBwdP p{g, g_bs, y, mean, invstd, gamma, beta, emask, emask_scale, C, H * W, cdiv(H * W, kChunk)};
   p.g_is_d = g_is_d;
   ProfScope ps(PF_BN_BWD, 0.0, (double)N * C * H * W * (12.0 + (emask && !g_is_d ? 1.0 : 0.0)), stream);     // the apply pass alone
@@ -913,7 +915,10 @@ extern "C" int wsl_bilinear_up2_fwd_amax(const float* u, float* out, int64_t out
                                          uint32_t* amax_slots, void* stream) {
   WSL_REQUIRE(u && out && N > 0 && C > 0 && h > 0 && w > 0, "bilinear_up2_fwd: bad args");
   WSL_REQUIRE(out_bs >= (int64_t)C * 4 * h * w, "bilinear_up2_fwd: out batch stride too small");
-  WSL_REQUIRE(!amax_slots || (ws && ws_bytes >= wsl_bilinear_up2_fwd_amax_ws_bytes(N, C, h, w)), "bilinear_up2_fwd_amax: workspace too small");
+  if (amax_slots && (!ws || ws_bytes < wsl_bilinear_up2_fwd_amax_ws_bytes(N, C, h, w))) {
+    set_error("bilinear_up2_fwd_amax: workspace %zu < %zu", ws ? ws_bytes : (size_t)0, wsl_bilinear_up2_fwd_amax_ws_bytes(N, C, h, w));
+    return WSL_EWORKSPACE;
+  }
   ProfScope ps(PF_BILINEAR, 0.0, 20.0 * (double)N * C * h * w, stream);            // read 4 B per input, write 4 x 4 B
   if (up2_fast_ok(out, out_bs, w) && (reinterpret_cast<uintptr_t>(u) & 15) == 0) {
     const dim3 grid(cdiv(2 * h, kUpFR), C, N);

@@ -1223,7 +1223,10 @@ extern "C" int wsl_sp_conv2d_wgrad_partial_amax(const WslSrc* a, const WslSrc* b
   const int Cb = (b && b->C > 0) ? b->C : 0, Ci = a->C + Cb;
   const WgSpPlan g = wgrad_sp_plan(N, H, W, a->C, Cb, Co);
   WSL_REQUIRE(g.ok, "sp_conv2d_wgrad_partial: no tile shape for %d x %d", H, W);
-  const size_t need = sizeof(float) * (size_t)g.splits * ((size_t)9 * Co * Ci + Co);
+  // checked against the query (an upper bound over both channel blockings, so >= what this launch writes): a workspace smaller than
+  // wsl_sp_conv2d_wgrad_ws_bytes() is refused whichever blocking the sources take
+  const size_t used = sizeof(float) * (size_t)g.splits * ((size_t)9 * Co * Ci + Co), query = wsl_sp_conv2d_wgrad_ws_bytes(N, H, W, Ci, Co);
+  const size_t need = used > query ? used : query;
   if (ws_bytes < need) {
     set_error("sp_conv2d_wgrad_partial: workspace %zu < %zu", ws_bytes, need);
     return WSL_EWORKSPACE;

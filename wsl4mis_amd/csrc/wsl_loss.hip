@@ -1029,13 +1029,29 @@ static int grid_for(int64_t n) {
 
 using namespace wsl;
 
+// Floats in front of the free part of the workspace: the head's partials and its 64 coefficients (`scal`), which every fused entry point
+// keeps alive between its passes.
+constexpr size_t kHeadFloats = (size_t)kMaxBlocks * kMaxK + 64;
+
+// Workgroups per sample the GatedCRF kernels can launch on an image of HW pixels, whatever its aspect ratio: the generic kernel's
+// cdiv(W, 32) * cdiv(H, 8) tiles (the 4-class kernel's 32 x 32 tiles are never more).  W <= 32: one tile column, cdiv(H, 8) <= cdiv(HW, 8);
+// W >= 33: cdiv(W, 32) < W / 16 and cdiv(H, 8) <= H, so the product stays below HW / 16.  Reached by a one-pixel-wide image.
+static size_t crf_max_tiles(int HW) { return ((size_t)HW + 7) / 8; }
+
 extern "C" size_t wsl_loss_ws_bytes(int N, int C, int HW) {
   if (N <= 0 || C <= 0 || HW <= 0) return 0;
-  const size_t tiles = (size_t)N * C * ((HW + 255) / 256 + 64);  // generous bound on 16x16 tile counts (any aspect)
+  // 16 x 16 tile counts of the pixel-tiled kernels (TV): cdiv(W, 16) * cdiv(H, 16) <= cdiv(HW, 16) <= 48 * (cdiv(HW, 256) + 64) for any
+  // aspect ratio, i.e. one float per tile fits the kMaxK floats per entry reserved here
+  const size_t tiles = (size_t)N * C * ((HW + 255) / 256 + 64);
   const size_t part = (tiles > (size_t)kMaxBlocks ? tiles : (size_t)kMaxBlocks) * kMaxK;
-  // + a region of its own for the GatedCRF partials (2 per tile of >= 256 pixels) when the CRF runs between the two passes of
-  //   the fused head (wsl_head_gatedcrf_fwd_bwd): the head's coefficients must survive it
-  return sizeof(float) * (part + 64 + (size_t)N * ((HW + 4095) / 4096) * (kMaxC + 1) + 2 * (size_t)N * ((HW + 255) / 256 + 64));
+  // [part][scal: 64][Mumford-Shah moments][2 * N * (cdiv(HW, 256) + 64): spare room of the large-layout regulariser partials]
+  const size_t base = part + 64 + (size_t)N * ((HW + 4095) / 4096) * (kMaxC + 1) + 2 * (size_t)N * ((HW + 255) / 256 + 64);
+  // the GatedCRF partials (2 per workgroup) live behind the head's coefficients when the CRF runs between the two passes of the fused
+  // head (wsl_head_gatedcrf_fwd_bwd); the query does not know the aspect ratio, so it holds the worst one (narrow images launch up to
+  // cdiv(HW, 8) workgroups per sample).  Only small problems (and C = 1) grow by this: from N * C * (cdiv(HW, 256) + 64) > kMaxBlocks on,
+  // `part` alone is 0.1875 * C floats per pixel against the 0.25 needed here.
+  const size_t crf = kHeadFloats + 2 * (size_t)N * crf_max_tiles(HW);
+  return sizeof(float) * (base > crf ? base : crf);
 }
 
 #define WSL_WS_OK(fn)                                                              \
@@ -1222,6 +1238,15 @@ extern "C" int wsl_head_gatedcrf_fwd_bwd(const float* z1, const float* z2, const
   WSL_REQUIRE(z2 == nullptr || dz2 != nullptr, "head_gatedcrf_fwd_bwd: dz2 missing");
   const int HW = H * W, HW_ = HW;
   WSL_WS_OK("head_gatedcrf_fwd_bwd");
+  // the GatedCRF partials (2 floats per workgroup) live behind the head's coefficients.  wsl_loss_ws_bytes holds the worst aspect ratio;
+  // the bound is checked here against this launch's real workgroup count, not assumed -- before anything is launched: a refused call
+  // writes nothing
+  const size_t crf_wg = (size_t)N * cdiv(W, kCrfTW) * cdiv(H, kCrfTH);
+  if (kHeadFloats + 2 * crf_wg > ws_bytes / sizeof(float)) {
+    set_error("head_gatedcrf_fwd_bwd: workspace %zu < %zu (GatedCRF partials of %d x %d x %d: %zu workgroups)", ws_bytes,
+              sizeof(float) * (kHeadFloats + 2 * crf_wg), N, H, W, crf_wg);
+    return WSL_EWORKSPACE;
+  }
   HeadP h{z1, z2, label, ignore, C, HW, N, (int64_t)N * HW, (float)beta, (float)(1.0 - beta)};
   const int nb = grid_for(h.P);
   float* part = static_cast<float*>(ws);
@@ -1231,8 +1256,9 @@ extern "C" int wsl_head_gatedcrf_fwd_bwd(const float* z1, const float* z2, const
     ProfScope ps(PF_LOSS_HEAD, 0.0, (double)N * HW * (4.0 * C * nbr + 1.0 + 4.0 * C), stream);
     head_stage1(h, nullptr, y, 0.f, out, C, N, z2 ? 1 : 0, part, scal, nb, stream);
   }
-  // the CRF's partials go behind the head's coefficients (the last region of wsl_loss_ws_bytes), which the backward pass needs
-  float* crf_part = static_cast<float*>(ws) + (ws_bytes / sizeof(float) - 2 * (size_t)N * ((HW + 255) / 256 + 64));
+  // the CRF's partials go right behind the head's coefficients, which the backward pass needs: ws[kHeadFloats ..), a fixed offset (the
+  // answer does not depend on how much larger than the query the caller's workspace is); the room was checked before the first launch
+  float* crf_part = scal + 64;
   if (int rc = gatedcrf_fwd_impl(y, img, msg, out + 4, N, C, H, W, radius, sigma_xy, sigma_rgb, weight, crf_part, stream)) return rc;
   {
     ProfScope ps(PF_LOSS_HEAD, 0.0, (double)N * HW * (4.0 * C * nbr + 1.0 + 4.0 * C + 4.0 * C * nbr), stream);
@@ -1256,13 +1282,19 @@ extern "C" int wsl_head_reg_fwd_bwd(const float* z, const uint8_t* label, int ig
   // the regulariser's partial sums: the head's own partials (ws[0 .. kMaxBlocks * kMaxK)) are dead once its finalize kernel ran, but its
   // coefficients `scal` right behind them (and the Mumford-Shah moments behind those) must survive until the last pass -- small
   // problems re-use the head's region, large ones (more TV tiles than it holds) the rest of the workspace behind the moments.
-  // Workspace layout (wsl_loss_ws_bytes, floats): [part: max(tiles, kMaxBlocks) * kMaxK][scal: 64][mom: N * chunks * (kMaxC + 1)][CRF /
-  // large-layout regulariser partials: 2 * N * (HW / 256 + 64)] -- the bound is checked below, not assumed
+  // Workspace layout (wsl_loss_ws_bytes, floats): [part: max(tiles, kMaxBlocks) * kMaxK, of which the head uses the first kMaxBlocks * kMaxK]
+  // [scal: 64, at the FIXED offset kMaxBlocks * kMaxK][mom: N * chunks * (kMaxC + 1)][everything behind the moments up to ws_bytes: the
+  // large-layout regulariser partials] -- the bound is checked below, not assumed.  (wsl_head_gatedcrf_fwd_bwd, which has no moments, puts
+  // its GatedCRF partials at the same offset as `mom`.)
   const int chunks = cdiv(HW, 4096);
   float* mom = scal + 64;
   const size_t rneed = (size_t)N * C * cdiv(W, 16) * cdiv(H, 16) + (size_t)N * chunks * 2 + kMaxBlocks;
   float* rpart = rneed <= (size_t)kMaxBlocks * kMaxK ? part : mom + (size_t)N * chunks * (kMaxC + 1);
-  WSL_REQUIRE((size_t)(rpart - part) + rneed <= ws_bytes / sizeof(float), "head_reg_fwd_bwd: workspace too small for the regulariser's partials");
+  if ((size_t)(rpart - part) + rneed > ws_bytes / sizeof(float)) {
+    set_error("head_reg_fwd_bwd: workspace %zu < %zu (the regulariser's partials of %d x %d x %d x %d)", ws_bytes,
+              sizeof(float) * ((size_t)(rpart - part) + rneed), N, C, H, W);
+    return WSL_EWORKSPACE;
+  }
   {   // pass 1: softmax (kept in s), partial-CE sums -> the head's coefficients
     ProfScope ps(PF_LOSS_HEAD, 0.0, (double)N * HW * (4.0 * C + 1.0 + 4.0 * C), stream);
     head_stage1(h, nullptr, s, 0.f, out, C, N, 0, part, scal, nb, stream);
