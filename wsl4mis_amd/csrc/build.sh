@@ -21,7 +21,7 @@ HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 srcs=(wsl_api wsl_conv wsl_conv2 wsl_conv4 wsl_conv5 wsl_convsp wsl_bn wsl_convt wsl_loss wsl_optim wsl_net wsl_data wsl_dil wsl_pnet)
 export LC_ALL=C
 SRC_SHA="$(cat $(ls "$here"/*.hip "$here"/*.h | sort) "$root/include/wsl_hip.h" | sha256sum | cut -d' ' -f1)"
-HDR_SHA="$(cat "$here/wsl_rt.h" "$here/wsl_debug.h" "$root/include/wsl_hip.h" | sha256sum | cut -d' ' -f1)"
+HDR_SHA="$(cat $(ls "$here"/*.h | sort) "$root/include/wsl_hip.h" | sha256sum | cut -d' ' -f1)"   # every private header: none can be forgotten
 
 # build_variant <object dir> <output .so> <compiler> <link flags> <extra header for the key> <compile flags...>
 build_variant() {

@@ -632,7 +632,7 @@ extern "C" int wsl_conv2d_fast_ok(const WslSrc* a, const WslSrc* b, const float*
 extern "C" int wsl_conv2d_stat_blocks(int N, int H, int W, int Ci, int Co, int ks) {
   if (N <= 0 || H <= 0 || W <= 0 || Co <= 0) return 0;
   const FwdPlan f = fwd_plan(N, H, W, Co, Ci, ks);
-  // one partial per tile; the (opt-in) wave-specialised kernel emits one per MFMA wave = four slots per tile
+  // one partial per tile
   return N * cdiv(H, f.th) * cdiv(W, f.tw);
 }
 
@@ -917,17 +917,15 @@ extern "C" int wsl_conv2d_wgrad(const WslSrc* a, const WslSrc* b, const float* d
   WslWgradPending q;
   if (int rc = wgrad_stage1(a, b, dy, dy_bs, dw, db, N, H, W, Co, ks, ws, ws_bytes, stream, &q)) return rc;
   const int KK = q.KK, Ci = q.Ci;
-  struct { int nsplit; } g{q.nsplit};
-  struct { const float* part_dw; const float* part_db; } p{q.part_dw, q.part_db};
   const int64_t total = (int64_t)KK * Co * Ci + (db ? Co : 0);
-  void* tok = prof_begin(PF_WGRAD_REDUCE, 0.0, 4.0 * (double)total * (g.nsplit + 1), stream);
+  void* tok = prof_begin(PF_WGRAD_REDUCE, 0.0, 4.0 * (double)total * (q.nsplit + 1), stream);
   struct EndProf { void* t; void* s; ~EndProf() { prof_end(t, s); } } endprof{tok, stream};
-  if (g.nsplit >= 64) {
-    WSL_LAUNCH((wgrad_reduce_kernel<16>), dim3((unsigned)((total + 15) / 16)), dim3(kThreads), 0, stream, p.part_dw,
-               p.part_db, dw, db, Co, Ci, KK, g.nsplit);
+  if (q.nsplit >= 64) {
+    WSL_LAUNCH((wgrad_reduce_kernel<16>), dim3((unsigned)((total + 15) / 16)), dim3(kThreads), 0, stream, q.part_dw,
+               q.part_db, dw, db, Co, Ci, KK, q.nsplit);
   } else {
-    WSL_LAUNCH((wgrad_reduce_kernel<4>), dim3((unsigned)((total + 63) / 64)), dim3(kThreads), 0, stream, p.part_dw,
-               p.part_db, dw, db, Co, Ci, KK, g.nsplit);
+    WSL_LAUNCH((wgrad_reduce_kernel<4>), dim3((unsigned)((total + 63) / 64)), dim3(kThreads), 0, stream, q.part_dw,
+               q.part_db, dw, db, Co, Ci, KK, q.nsplit);
   }
   return check_launch("wgrad_reduce_kernel");
 }

@@ -21,12 +21,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 
-#include "wsl_rt.h"
-
-#define WSL_TRY(expr)                 \
-  do {                                \
-    if (int rc_ = (expr)) return rc_; \
-  } while (0)
+#include "wsl_seq.h"
 
 namespace wsl {
 

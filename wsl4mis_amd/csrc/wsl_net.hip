@@ -5,11 +5,9 @@
 // What is kept in HBM between forward and backward: the raw (pre-BatchNorm) output of every convolution, the pooled
 // encoder inputs, the 1x1-conv / upsampled decoder tensors and 4*C BatchNorm coefficients per layer.  Normalised /
 // activated / dropped-out / concatenated tensors are never materialised: consumers rebuild them while staging tiles.
-#include <stdio.h>
-#include <string.h>
 #include <initializer_list>
 
-#include "wsl_rt.h"
+#include "wsl_seq.h"
 
 namespace wsl {
 
@@ -18,11 +16,8 @@ int sp_pack_table(const PackTable& t, const int64_t* img_off_bytes, const float*
 
 static const int kFt[5] = {16, 32, 64, 128, 256};            // unet.py:291
 static const float kDrop[5] = {0.05f, 0.1f, 0.2f, 0.3f, 0.5f};  // unet.py:292
-static const float kEps = 1e-5f, kMom = 0.1f;
 constexpr int kSpMaxLayers = 40;   // = PackTable's capacity: conv layers of one network (36 in unet_cct)
 
-struct ConvRef { int64_t w, b; int Ci, Co, ks; int li; };   // li: index in the pack table
-struct BnRef { int64_t gamma, beta, rmean, rvar; int nbt, C; };
 struct BlockRef { ConvRef c1, c2; BnRef b1, b2; };
 struct BlkWs { size_t y1, y2, st1, st2; };  // st*: mean | invstd | scale | shift (4*C floats)
 
@@ -53,33 +48,38 @@ struct Plan {
   bool want_regions = false, regs_overflow = false;
 };
 
-struct Bump {
-  size_t off = 0;
-  size_t take(size_t n) {
-    const size_t o = off;
-    off += (n + 63) & ~(size_t)63;
-    return o;
-  }
-};
-
-static void plan_conv(ConvRef& c, int Ci, int Co, int ks, int64_t& po) {
-  c.Ci = Ci, c.Co = Co, c.ks = ks;
-  c.w = po, po += (int64_t)Co * Ci * ks * ks;
-  c.b = po, po += Co;
-}
-static void plan_bn(BnRef& b, int C, int64_t& po, int64_t& bo, int64_t& nbn) {
-  b.C = C;
-  b.gamma = po, po += C;
-  b.beta = po, po += C;
-  b.rmean = bo, bo += C;
-  b.rvar = bo, bo += C;
-  b.nbt = (int)nbn++;
-}
 static void plan_block(BlockRef& k, int Ci, int Co, int64_t& po, int64_t& bo, int64_t& nbn) {
   plan_conv(k.c1, Ci, Co, 3, po);
   plan_bn(k.b1, Co, po, bo, nbn);
   plan_conv(k.c2, Co, Co, 3, po);
   plan_bn(k.b2, Co, po, bo, nbn);
+}
+
+// one 3x3 layer at level l: grows the statistics scratch to its tile count `nb` (f32 plan, and the split plan's when it is on) and
+// returns the bytes of its weight-gradient partials (256-aligned: every layer of a phase keeps a region of its own)
+static size_t layer_need(const Plan& P, const ConvRef& c, int l, size_t& max_stat, size_t& max_cnt, size_t& nb) {
+  const int N = P.d.N, H = P.H[l], W = P.W[l];
+  nb = wsl_conv2d_stat_blocks(N, H, W, c.Ci, c.Co, 3);
+  size_t wgb = wsl_conv2d_wgrad_ws_bytes(N, H, W, c.Ci, c.Co, 3);
+  if (P.sp) {
+    const size_t nb2 = wsl_sp_conv2d_stat_blocks(N, H, W, c.Ci, c.Co);
+    const size_t wgb2 = wsl_sp_conv2d_wgrad_ws_bytes(N, H, W, c.Ci, c.Co);
+    nb = nb2 > nb ? nb2 : nb, wgb = wgb2 > wgb ? wgb2 : wgb;
+  }
+  if (nb * c.Co * 2 > max_stat) max_stat = nb * c.Co * 2;
+  if (nb > max_cnt) max_cnt = nb;
+  return (wgb + 255) & ~(size_t)255;
+}
+
+// one scratch set: three gradient tensors of `big` floats, two of `small`, then what P.wg_bytes / bn_bytes / bn_coef_bytes ask for
+template <class B>
+static void plan_scratch(B& b, Plan& P, int k, size_t big, size_t small, size_t max_stat, size_t max_cnt) {
+  Plan::Scratch& S = P.scr[k];
+  S.tmp_g = b.take(big, "tmp_g"), S.tmp_g1 = b.take(big, "tmp_g1"), S.tmp_dy = b.take(big, "tmp_dy");
+  S.tmp_du = b.take(small, "tmp_du"), S.tmp_gpool = b.take(small, "tmp_gpool");
+  S.stat_part = b.take(max_stat, "stat_part"), S.stat_cnt = b.take(max_cnt, "stat_cnt");
+  S.wg_ws = b.take((P.wg_bytes + 3) / 4, "wg_ws"), S.bn_ws = b.take((P.bn_bytes + 3) / 4, "bn_ws");
+  S.bn_coef = b.take((P.bn_coef_bytes + 3) / 4, "bn_coef");
 }
 
 static int make_plan(const WslNetDesc* d, Plan& P) {
@@ -150,8 +150,8 @@ static int make_plan(const WslNetDesc* d, Plan& P) {
     w.y1 = B.take(e, "y1"), w.y2 = B.take(e, "y2");
     w.st1 = B.take(4 * k.c1.Co, "st1"), w.st2 = B.take(4 * k.c1.Co, "st2");
     for (const ConvRef* c : {&k.c1, &k.c2}) {
-      size_t nb = wsl_conv2d_stat_blocks(d->N, P.H[l], P.W[l], c->Ci, c->Co, 3);
-      size_t wgb = wsl_conv2d_wgrad_ws_bytes(d->N, P.H[l], P.W[l], c->Ci, c->Co, 3);
+      size_t nb;
+      *wg_acc += layer_need(P, *c, l, max_stat, max_cnt, nb);
       // BatchNorm-backward statistics arrive as one partial per tile of whichever kernel produces the gradient: the data gradient
       // of this layer's consumer (tile counts of the f32 and of the split plans, for either channel count) or the fan-in kernel
       size_t nbb = nb;
@@ -159,14 +159,6 @@ static int make_plan(const WslNetDesc* d, Plan& P) {
         const size_t a = wsl_conv2d_stat_blocks(d->N, P.H[l], P.W[l], c->Co, co_alt, 3), a1 = wsl_conv2d_stat_blocks(d->N, P.H[l], P.W[l], c->Co, co_alt, 1);
         nbb = a > nbb ? a : nbb, nbb = a1 > nbb ? a1 : nbb;
       }
-      if (P.sp) {
-        const size_t nb2 = wsl_sp_conv2d_stat_blocks(d->N, P.H[l], P.W[l], c->Ci, c->Co);
-        const size_t wgb2 = wsl_sp_conv2d_wgrad_ws_bytes(d->N, P.H[l], P.W[l], c->Ci, c->Co);
-        nb = nb2 > nb ? nb2 : nb, wgb = wgb2 > wgb ? wgb2 : wgb, nbb = nb2 > nbb ? nb2 : nbb;
-      }
-      if (nb * c->Co * 2 > max_stat) max_stat = nb * c->Co * 2;
-      if (nb > max_cnt) max_cnt = nb;
-      wg_add(*wg_acc, wgb);
       const size_t fan = wsl_feat_grad_combine_blocks(d->N, P.H[l], P.W[l]);
       nbb = fan > nbb ? fan : nbb;
       const size_t pb = sizeof(float) * (nbb * c->Co * 2 + 2 * (size_t)c->Co);
@@ -208,13 +200,8 @@ static int make_plan(const WslNetDesc* d, Plan& P) {
       if (b > P.bn_coef_bytes) P.bn_coef_bytes = b;
     }
   for (int k = 0; k < d->n_dec; ++k) {
-    Plan::Scratch& S = P.scr[k];
     B.tag = "scratch", B.i0 = k, B.i1 = 0;
-    S.tmp_g = B.take(big, "tmp_g"), S.tmp_g1 = B.take(big, "tmp_g1"), S.tmp_dy = B.take(big, "tmp_dy");
-    S.tmp_du = B.take(big / 4, "tmp_du"), S.tmp_gpool = B.take(big / 4, "tmp_gpool");
-    S.stat_part = B.take(max_stat, "stat_part"), S.stat_cnt = B.take(max_cnt, "stat_cnt");
-    S.wg_ws = B.take((P.wg_bytes + 3) / 4, "wg_ws"), S.bn_ws = B.take((P.bn_bytes + 3) / 4, "bn_ws");
-    S.bn_coef = B.take((P.bn_coef_bytes + 3) / 4, "bn_coef");
+    plan_scratch(B, P, k, big, big / 4, max_stat, max_cnt);
   }
   if (d->n_dec == 1) P.scr[1] = P.scr[0];
   B.tag = "images", B.i0 = 0, B.i1 = 0;
@@ -232,11 +219,6 @@ static int make_plan(const WslNetDesc* d, Plan& P) {
 }
 
 // ------------------------------------------------------------------------------------------------ helpers
-#define WSL_TRY(expr)           \
-  do {                          \
-    if (int rc_ = (expr)) return rc_; \
-  } while (0)
-
 struct Ctx {
   const Plan& P;
   const float* params;
@@ -247,15 +229,8 @@ struct Ctx {
   void* stream;
   int training;
   int si = 0;   // scratch set
-  struct WgBatch* wb = nullptr;   // weight gradients whose second stage is pending (one launch per phase)
+  WgBatch* wb = nullptr;   // weight gradients whose second stage is pending (one launch per phase)
   const Plan::Scratch& S() const { return P.scr[si]; }
-};
-
-// pending second stages of a phase (a decoder's backward, the encoder's backward) + the bump pointer into the set's wg_ws
-struct WgBatch {
-  WslWgradPending items[24];
-  int n = 0;
-  size_t off = 0;   // bytes
 };
 
 // weight gradient of one layer: stage 1 now (its partials get their own region of wg_ws), stage 2 with the phase's batch
@@ -268,38 +243,15 @@ static int wgrad_layer(const Ctx& c, const WslSrc* a, const WslSrc* b, const flo
                   !(reinterpret_cast<uintptr_t>(dy) & 15) && !(dy_bs & 3) && Co % 32 == 0 && a->C % 32 == 0 && (!b || b->C % 32 == 0);
   const size_t need = ((sp ? wsl_sp_conv2d_wgrad_ws_bytes(N, H, W, Ci, Co) : wsl_conv2d_wgrad_ws_bytes(N, H, W, Ci, Co, ks)) + 255) &
                       ~(size_t)255;
-  WgBatch* wb = c.wb;
-  if (!wb || wb->n >= 24 || wb->off + need > c.P.wg_bytes) {
-    set_error("net: weight-gradient batch overflow (%d pending, %zu + %zu of %zu bytes)", wb ? wb->n : -1, wb ? wb->off : 0, need,
-              c.P.wg_bytes);
-    return WSL_EWORKSPACE;
-  }
-  char* ws = reinterpret_cast<char*>(c.ws + c.S().wg_ws) + wb->off;
-  if (sp) WSL_TRY(wsl_sp_conv2d_wgrad_partial_amax(a, b, dy, dy_bs, dy_amax, raw_amax, dw, db, N, H, W, Co, ws, need, &wb->items[wb->n], c.stream));
-  else WSL_TRY(wsl_conv2d_wgrad_partial(a, b, dy, dy_bs, dw, db, N, H, W, Co, ks, ws, need, &wb->items[wb->n], c.stream));
-  wb->n += 1, wb->off += need;
-  return WSL_OK;
-}
-static int wgrad_flush(const Ctx& c) {
-  WgBatch* wb = c.wb;
-  if (!wb || wb->n == 0) return WSL_OK;
-  const int rc = wsl_wgrad_reduce_batch(wb->items, wb->n, c.stream);
-  wb->n = 0, wb->off = 0;
-  return rc;
+  return wgrad_push(c.wb, "net", c.ws + c.S().wg_ws, need, [&](void* ws, size_t n, WslWgradPending* q) {
+    return sp ? wsl_sp_conv2d_wgrad_partial_amax(a, b, dy, dy_bs, dy_amax, raw_amax, dw, db, N, H, W, Co, ws, n, q, c.stream)
+              : wsl_conv2d_wgrad_partial(a, b, dy, dy_bs, dw, db, N, H, W, Co, ks, ws, n, q, c.stream);
+  });
 }
 
-static WslSrc raw_src(const float* x, int C, int64_t bs) {
-  WslSrc s{};
-  s.x = x, s.C = C, s.bs = bs, s.emask_scale = 1.f;
-  return s;
-}
-// virtual tensor leaky(bn(y)) [* emask] [* cmask]
+// virtual tensor leaky(bn(y)) [* emask] [* cmask] of the dense raw conv output ws[y] with the BatchNorm coefficients ws[st]
 static WslSrc act_src(const Ctx& c, size_t y, size_t st, int C, int HW, const uint8_t* emask, float es, const float* cmask) {
-  WslSrc s{};
-  s.x = c.ws + y, s.C = C, s.bs = (int64_t)C * HW;
-  s.scale = c.ws + st + 2 * C, s.shift = c.ws + st + 3 * C;
-  s.emask = emask, s.emask_scale = es, s.cmask = cmask;
-  return s;
+  return act_src(c.ws + y, C, (int64_t)C * HW, c.ws + st + 2 * C, c.ws + st + 3 * C, emask, es, cmask);
 }
 
 // split-precision path: float offset of a layer's weight image inside its arena (16-byte aligned, images never overlap: a 3x3
@@ -447,15 +399,10 @@ static int conv_bn_fwd(const Ctx& c, const ConvRef& cv, const BnRef& bn, const W
   float* stc = c.training ? c.ws + c.S().stat_cnt : nullptr;
   WSL_TRY(conv_any(c, cv, 0, a, b, c.params + cv.b, c.ws + y, (int64_t)C * H * W, H, W, stp, stc, raw_amax));
   float* s = c.ws + st;
-  if (c.training) {
-    const int nblk = sp_takes(c, cv, a, b, c.ws + y, (int64_t)C * H * W, H, W, C) ? wsl_sp_conv2d_stat_blocks(N, H, W, cv.Ci, C)
-                                                                                 : wsl_conv2d_stat_blocks(N, H, W, cv.Ci, C, cv.ks);
-    return wsl_bn_stats_finalize(stp, stc, nblk, C, c.params + bn.gamma, c.params + bn.beta, kEps, kMom,
-                                 c.buffers + bn.rmean, c.buffers + bn.rvar, c.nbt ? c.nbt + bn.nbt : nullptr, s, s + C,
-                                 s + 2 * C, s + 3 * C, c.stream);
-  }
-  return wsl_bn_eval_affine(c.params + bn.gamma, c.params + bn.beta, c.buffers + bn.rmean, c.buffers + bn.rvar, kEps, C,
-                            s + 2 * C, s + 3 * C, c.stream);
+  const int nblk = !c.training ? 0
+                   : sp_takes(c, cv, a, b, c.ws + y, (int64_t)C * H * W, H, W, C) ? wsl_sp_conv2d_stat_blocks(N, H, W, cv.Ci, C)
+                                                                                  : wsl_conv2d_stat_blocks(N, H, W, cv.Ci, C, cv.ks);
+  return bn_fwd(c.training, stp, stc, nblk, bn, c.params, c.buffers, c.nbt, s, s + C, s + 2 * C, s + 3 * C, c.stream);
 }
 
 static int block_fwd(const Ctx& c, const BlockRef& k, const BlkWs& w, const WslSrc* a, const WslSrc* b, int l,
@@ -554,7 +501,7 @@ static int decoder_bwd(const Ctx& c, int k, const float* const* cmasks, const fl
       WSL_TRY(conv_dgrad_bn(c, cv, du, g, h, w, P.wdec[k].blk[i - 1].y2, P.wdec[k].blk[i - 1].st2, nullptr, 1.f, &gs));
     }
   }
-  return wgrad_flush(c);   // second stage of this decoder's 13 weight gradients: one launch
+  return wgrad_flush(c.wb, c.stream);   // second stage of this decoder's 13 weight gradients: one launch
 }
 
 static int encoder_bwd(const Ctx& c, const float* x, const uint8_t* const* emasks, const float* const* cmasks) {
@@ -587,42 +534,18 @@ static int encoder_bwd(const Ctx& c, const float* x, const uint8_t* const* emask
     WSL_TRY(block_bwd(c, P.enc[l], P.wenc[l], &in, nullptr, l, emasks[l], 1.f / (1.f - kDrop[l]), g, (int64_t)C * H * W, gs,
                       l > 0 ? gpool : nullptr));
   }
-  return wgrad_flush(c);   // second stage of the encoder's 10 weight gradients: one launch
+  return wgrad_flush(c.wb, c.stream);   // second stage of the encoder's 10 weight gradients: one launch
 }
 
 }  // namespace wsl
 
 using namespace wsl;
 
-static void entry_set(WslNetEntry* e, const char* name, int kind, int ndim, int64_t s0, int64_t s1, int64_t s2, int64_t s3,
-                      int64_t off) {
-  memset(e, 0, sizeof(*e));
-  snprintf(e->name, sizeof(e->name), "%s", name);
-  e->kind = kind, e->ndim = ndim, e->offset = off;
-  e->shape[0] = s0, e->shape[1] = s1, e->shape[2] = s2, e->shape[3] = s3;
-}
-
 // state_dict order of the reference module (7 entries per conv+bn pair, see oracle/torch_ref.py:state_layout)
 static int enumerate_entries(const Plan& P, int want, WslNetEntry* out) {
-  int idx = 0;
-  char nm[128];
-  auto conv = [&](const char* pre, const char* sfx, const ConvRef& c) {
-    snprintf(nm, sizeof(nm), "%s%s.weight", pre, sfx);
-    if (idx++ == want) entry_set(out, nm, 0, 4, c.Co, c.Ci, c.ks, c.ks, c.w);
-    snprintf(nm, sizeof(nm), "%s%s.bias", pre, sfx);
-    if (idx++ == want) entry_set(out, nm, 0, 1, c.Co, 0, 0, 0, c.b);
-  };
-  auto bn = [&](const char* pre, const char* sfx, const BnRef& b) {
-    const char* f[5] = {"weight", "bias", "running_mean", "running_var", "num_batches_tracked"};
-    const int64_t off[5] = {b.gamma, b.beta, b.rmean, b.rvar, b.nbt};
-    const int kind[5] = {0, 0, 1, 1, 2};
-    for (int k = 0; k < 5; ++k) {
-      snprintf(nm, sizeof(nm), "%s%s.%s", pre, sfx, f[k]);
-      if (idx++ == want) entry_set(out, nm, kind[k], k == 4 ? 0 : 1, k == 4 ? 0 : b.C, 0, 0, 0, off[k]);
-    }
-  };
+  EntryWalk e{want, out};
   auto block = [&](const char* pre, const BlockRef& k) {
-    conv(pre, ".0", k.c1), bn(pre, ".1", k.b1), conv(pre, ".4", k.c2), bn(pre, ".5", k.b2);
+    e.conv(pre, ".0", k.c1), e.bn(pre, ".1", k.b1), e.conv(pre, ".4", k.c2), e.bn(pre, ".5", k.b2);
   };
   char pre[96];
   block("encoder.in_conv.conv_conv", P.enc[0]);
@@ -634,14 +557,14 @@ static int enumerate_entries(const Plan& P, int want, WslNetEntry* out) {
     const char* dn = P.d.n_dec == 1 ? "decoder" : (k == 0 ? "main_decoder" : "aux_decoder1");
     for (int i = 0; i < 4; ++i) {
       snprintf(pre, sizeof(pre), "%s.up%d.conv1x1", dn, i + 1);
-      conv(pre, "", P.dec[k].c1x1[i]);
+      e.conv(pre, "", P.dec[k].c1x1[i]);
       snprintf(pre, sizeof(pre), "%s.up%d.conv.conv_conv", dn, i + 1);
       block(pre, P.dec[k].blk[i]);
     }
     snprintf(pre, sizeof(pre), "%s.out_conv", dn);
-    conv(pre, "", P.dec[k].out);
+    e.conv(pre, "", P.dec[k].out);
   }
-  return idx;
+  return e.idx;
 }
 
 extern "C" int wsl_net_num_entries(const WslNetDesc* d) {
@@ -682,10 +605,7 @@ extern "C" int wsl_net_forward(const WslNetDesc* d, const float* params, float* 
   WSL_REQUIRE(params && buffers && x && logits_main && ws, "net_forward: null argument");
   WSL_REQUIRE(d->n_dec == 1 || (logits_aux && cmasks), "net_forward: unet_cct needs logits_aux and cmasks");
   WSL_REQUIRE(!training || emasks, "net_forward: training needs the 5 dropout keep-masks");
-  if (ws_bytes < P.total_floats * sizeof(float)) {
-    set_error("net_forward: workspace %zu < %zu", ws_bytes, P.total_floats * sizeof(float));
-    return WSL_EWORKSPACE;
-  }
+  WSL_TRY(check_ws("net_forward", ws_bytes, P.total_floats * sizeof(float)));
   Ctx c{P, params, buffers, nbt, nullptr, static_cast<float*>(ws), stream, training};
   const int N = d->N;
   WSL_TRY(pack_all(c, training));   // packed weight images; training also builds the data-gradient ones for the backward
@@ -725,12 +645,10 @@ extern "C" int wsl_net_backward(const WslNetDesc* d, const float* params, const 
   WSL_REQUIRE(params && x && emasks && grads && ws, "net_backward: null argument");
   WSL_REQUIRE(phase >= 0 && phase <= 2, "net_backward: phase %d", phase);
   WSL_REQUIRE(phase == 2 || (dlogits_main && (d->n_dec == 1 || (dlogits_aux && cmasks))), "net_backward: missing dlogits");
-  if (ws_bytes < P.total_floats * sizeof(float)) {
-    set_error("net_backward: workspace %zu < %zu", ws_bytes, P.total_floats * sizeof(float));
-    return WSL_EWORKSPACE;
-  }
+  WSL_TRY(check_ws("net_backward", ws_bytes, P.total_floats * sizeof(float)));
   Ctx c{P, params, nullptr, nullptr, grads, static_cast<float*>(ws), stream, 1};
   WgBatch wb0, wb1;
+  wb0.cap = wb1.cap = P.wg_bytes;
   c.wb = &wb0;
   if (phase == 0 || phase == 1) {
     void* side = d->n_dec == 2 ? side_stream(stream) : nullptr;
@@ -857,22 +775,13 @@ static int make_up_plan(const WslUpBlockDesc* d, UpPlan& U) {
   const size_t e = N * d->Co * HW;
   U.wblk.y1 = B.take(e), U.wblk.y2 = B.take(e), U.wblk.st1 = B.take(4 * d->Co), U.wblk.st2 = B.take(4 * d->Co);
   U.upt = B.take(N * d->C2 * HW), U.dcat = B.take(N * 2 * d->C2 * HW), U.tmp_out = B.take(e);
-  size_t max_stat = 0, max_cnt = 0, wg = 0;
-  for (const ConvRef* cv : {&U.blk.c1, &U.blk.c2}) {
-    const size_t nb = wsl_conv2d_stat_blocks(d->N, P.H[0], P.W[0], cv->Ci, cv->Co, 3);
-    if (nb * cv->Co * 2 > max_stat) max_stat = nb * cv->Co * 2;
-    if (nb > max_cnt) max_cnt = nb;
-    wg += (wsl_conv2d_wgrad_ws_bytes(d->N, P.H[0], P.W[0], cv->Ci, cv->Co, 3) + 255) & ~(size_t)255;
-  }
+  size_t max_stat = 0, max_cnt = 0, wg = 0, nb;
+  for (const ConvRef* cv : {&U.blk.c1, &U.blk.c2}) wg += layer_need(P, *cv, 0, max_stat, max_cnt, nb);
   const size_t ct = wsl_convt2x2_wgrad_ws_bytes(d->N, d->C1, d->C2);
   P.wg_bytes = wg > ct ? wg : ct;
   P.bn_bytes = wsl_bnact_bwd_ws_bytes(d->N, d->Co, P.H[0], P.W[0]);
-  Plan::Scratch& S = P.scr[0];
-  S.tmp_g = B.take(e), S.tmp_g1 = B.take(e), S.tmp_dy = B.take(e);
-  S.tmp_du = 0, S.tmp_gpool = 0;
-  S.stat_part = B.take(max_stat), S.stat_cnt = B.take(max_cnt);
-  S.wg_ws = B.take((P.wg_bytes + 3) / 4), S.bn_ws = B.take((P.bn_bytes + 3) / 4), S.bn_coef = B.take(2 * (size_t)d->Co + 64);
   P.bn_coef_bytes = sizeof(float) * (2 * (size_t)d->Co + 64);
+  plan_scratch(B, P, 0, e, 0, max_stat, max_cnt);   // (no upsampling / pooling gradients: tmp_du, tmp_gpool stay empty)
   P.scr[1] = P.scr[0];
   P.packf = B.take(P.n_param), P.packd = B.take(P.n_param);
   P.winof = B.take(2 * P.n_param), P.winod = B.take(2 * P.n_param);
@@ -908,10 +817,7 @@ extern "C" int wsl_upblock_t_forward(const WslUpBlockDesc* d, const float* param
   WSL_TRY(make_up_plan(d, U));
   WSL_REQUIRE(params && buffers && x1 && x2 && out && ws, "upblock_t_forward: null argument");
   WSL_REQUIRE(!(training && d->dropout_p > 0.f) || emask, "upblock_t_forward: training with dropout_p > 0 needs the keep mask");
-  if (ws_bytes < U.P.total_floats * sizeof(float)) {
-    set_error("upblock_t_forward: workspace %zu < %zu", ws_bytes, U.P.total_floats * sizeof(float));
-    return WSL_EWORKSPACE;
-  }
+  WSL_TRY(check_ws("upblock_t_forward", ws_bytes, U.P.total_floats * sizeof(float)));
   const Plan& P = U.P;
   Ctx c{P, params, buffers, nbt, nullptr, static_cast<float*>(ws), stream, training};
   const int H = P.H[0], W = P.W[0];
@@ -932,13 +838,11 @@ extern "C" int wsl_upblock_t_backward(const WslUpBlockDesc* d, const float* para
   UpPlan U;
   WSL_TRY(make_up_plan(d, U));
   WSL_REQUIRE(params && x1 && x2 && dout && grads && ws, "upblock_t_backward: null argument");
-  if (ws_bytes < U.P.total_floats * sizeof(float)) {
-    set_error("upblock_t_backward: workspace %zu < %zu", ws_bytes, U.P.total_floats * sizeof(float));
-    return WSL_EWORKSPACE;
-  }
+  WSL_TRY(check_ws("upblock_t_backward", ws_bytes, U.P.total_floats * sizeof(float)));
   const Plan& P = U.P;
   Ctx c{P, params, nullptr, nullptr, grads, static_cast<float*>(ws), stream, 1};
   WgBatch wb;
+  wb.cap = P.wg_bytes;
   c.wb = &wb;
   const int H = P.H[0], W = P.W[0];
   const int64_t HW = (int64_t)H * W;
@@ -947,7 +851,7 @@ extern "C" int wsl_upblock_t_backward(const WslUpBlockDesc* d, const float* para
   const float es = d->dropout_p > 0.f ? 1.f / (1.f - d->dropout_p) : 1.f;
   float* dcat = c.ws + U.dcat;
   WSL_TRY(block_bwd(c, U.blk, U.wblk, &skip, &up, 0, d->dropout_p > 0.f ? emask : nullptr, es, dout, U.Co * HW, GStats{}, dcat));
-  WSL_TRY(wgrad_flush(c));
+  WSL_TRY(wgrad_flush(c.wb, c.stream));
   const float* dup = dcat + U.C2 * HW;       // d(cat)[:, C2:] = gradient of the transposed convolution's output
   WSL_TRY(wsl_convt2x2_wgrad(x1, dup, 2 * U.C2 * HW, grads + U.up.w, grads + U.up.b, d->N, U.C1, U.C2, U.h, U.w,
                              c.ws + c.S().wg_ws, P.wg_bytes, stream));

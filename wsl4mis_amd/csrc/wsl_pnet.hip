@@ -7,51 +7,24 @@
 // source whose BatchNorm tables are the five in2 tables laid end to end.  No BatchNorm / LeakyReLU output is materialised: the
 // LeakyReLU-only sites (catblock and out.conv1 outputs) go through the loader with unit scale and zero shift, the two Dropout2d sites
 // as its channel multiplier.
-#include <stdio.h>
-#include <string.h>
-
-#include "wsl_rt.h"
-
-#define WSL_TRY(expr)                 \
-  do {                                \
-    if (int rc_ = (expr)) return rc_; \
-  } while (0)
+#include "wsl_seq.h"
 
 namespace wsl {
 namespace {
 
-const float kEps = 1e-5f, kMom = 0.1f;
-
-struct PConv { int64_t w, b; int Ci, Co, ks; };
-struct PBn { int64_t gamma, beta, rmean, rvar; int nbt; };
-struct PBlock { PConv c1, c2; PBn b1, b2; int dil; };
+struct PBlock { ConvRef c1, c2; BnRef b1, b2; int dil; };
 
 struct PPlan {
   WslPNetDesc d;
   int F;
   int64_t HW, NHW;
   PBlock blk[5];
-  PConv cb1, cb2, o1, o2;
+  ConvRef cb1, cb2, o1, o2;
   int64_t n_param, n_block_param, n_buf;
   // workspace (float offsets)
   size_t cat, y1[5], st1[5], st2, zc1, zc2, zo1, unit, stat_part, stat_cnt, bufA, bufB, ycopy, bn_ws, wg_ws;
   size_t bn_bytes, wg_bytes[2], total_floats;
 };
-
-struct PBump {
-  size_t off = 0;
-  size_t take(size_t n) {
-    const size_t o = off;
-    off += (n + 63) & ~(size_t)63;
-    return o;
-  }
-};
-
-static void plan_conv(PConv& c, int Ci, int Co, int ks, int64_t& po) {
-  c.Ci = Ci, c.Co = Co, c.ks = ks;
-  c.w = po, po += (int64_t)Co * Ci * ks * ks;
-  c.b = po, po += Co;
-}
 
 static int make_plan(const WslPNetDesc* d, PPlan& P) {
   WSL_REQUIRE(d, "pnet: null descriptor");
@@ -63,20 +36,14 @@ static int make_plan(const WslPNetDesc* d, PPlan& P) {
   P.F = F;
   P.HW = (int64_t)d->H * d->W, P.NHW = (int64_t)d->N * P.HW;
   // parameters() order: per block conv1, conv2, in1, in2 (registration order of PNetBlock), then catblock, then out
-  int64_t po = 0, bo = 0;
+  int64_t po = 0, bo = 0, nbn = 0;
   for (int k = 0; k < 5; ++k) {
     PBlock& b = P.blk[k];
     b.dil = d->ratios[k];
     plan_conv(b.c1, k == 0 ? d->in_chns : F, F, 3, po);
     plan_conv(b.c2, F, F, 3, po);
-    PBn* bn[2] = {&b.b1, &b.b2};
-    for (int i = 0; i < 2; ++i) {
-      bn[i]->gamma = po, po += F;
-      bn[i]->beta = po, po += F;
-      bn[i]->rmean = bo, bo += F;
-      bn[i]->rvar = bo, bo += F;
-      bn[i]->nbt = 2 * k + i;
-    }
+    plan_bn(b.b1, F, po, bo, nbn);   // (num_batches_tracked slots 2k, 2k + 1)
+    plan_bn(b.b2, F, po, bo, nbn);
   }
   P.n_block_param = po;
   plan_conv(P.cb1, 5 * F, 5 * F, 1, po);
@@ -87,7 +54,7 @@ static int make_plan(const WslPNetDesc* d, PPlan& P) {
 
   const int N = d->N, H = d->H, W = d->W;
   const size_t u = (size_t)P.NHW * F;   // one [N,F,H,W] tensor
-  PBump B;
+  Bump B;
   P.cat = B.take(5 * u);
   for (int k = 0; k < 5; ++k) P.y1[k] = B.take(u);
   for (int k = 0; k < 5; ++k) P.st1[k] = B.take(4 * (size_t)F);
@@ -157,12 +124,6 @@ static unsigned ew_grid(int64_t total) {
 }
 
 // ------------------------------------------------------------------------------------------------ sequencing
-struct PWgBatch {
-  WslWgradPending items[16];
-  int n = 0;
-  size_t off = 0;   // bytes
-};
-
 struct PCtx {
   const PPlan& P;
   const float* params;
@@ -172,46 +133,31 @@ struct PCtx {
   float* ws;
   void* stream;
   int training;
-  PWgBatch* wb;
-  size_t wb_cap;
+  WgBatch* wb;
 };
 
-static WslSrc raw_src(const float* x, int C, int64_t bs) {
-  WslSrc s{};
-  s.x = x, s.C = C, s.bs = bs, s.emask_scale = 1.f;
-  return s;
-}
-static WslSrc act_src(const float* y, int C, int64_t bs, const float* scale, const float* shift, const float* cmask) {
-  WslSrc s = raw_src(y, C, bs);
-  s.scale = scale, s.shift = shift, s.cmask = cmask;
-  return s;
-}
+// (no element mask anywhere in this network: its two dropout sites are Dropout2d, the loader's channel multiplier)
 // virtual tensor leaky(z) [* cmask] of a dense [N,C,H,W] tensor
 static WslSrc leaky_src(const PCtx& c, size_t z, int C, const float* cmask) {
   const int F5 = 5 * c.P.F;
-  return act_src(c.ws + z, C, (int64_t)C * c.P.HW, c.ws + c.P.unit, c.ws + c.P.unit + F5, cmask);
+  return act_src(c.ws + z, C, (int64_t)C * c.P.HW, c.ws + c.P.unit, c.ws + c.P.unit + F5, nullptr, 1.f, cmask);
 }
 // block k's output f_k = leaky(in2(y2_k)): slice k of the concat buffer
 static WslSrc block_out_src(const PCtx& c, int k) {
   const PPlan& P = c.P;
   const int F = P.F;
   return act_src(c.ws + P.cat + (size_t)k * F * P.HW, F, 5 * F * P.HW, c.ws + P.st2 + 10 * F + k * F, c.ws + P.st2 + 15 * F + k * F,
-                 nullptr);
+                 nullptr, 1.f, nullptr);
 }
 static WslSrc block_mid_src(const PCtx& c, int k) {
   const PPlan& P = c.P;
   const int F = P.F;
-  return act_src(c.ws + P.y1[k], F, F * P.HW, c.ws + P.st1[k] + 2 * F, c.ws + P.st1[k] + 3 * F, nullptr);
+  return act_src(c.ws + P.y1[k], F, F * P.HW, c.ws + P.st1[k] + 2 * F, c.ws + P.st1[k] + 3 * F, nullptr, 1.f, nullptr);
 }
 
-static int bn_fwd(const PCtx& c, const PBn& bn, int nblk, float* mean, float* invstd, float* scale, float* shift) {
-  const PPlan& P = c.P;
-  if (c.training)
-    return wsl_bn_stats_finalize(c.ws + P.stat_part, c.ws + P.stat_cnt, nblk, P.F, c.params + bn.gamma, c.params + bn.beta, kEps, kMom,
-                                 c.buffers + bn.rmean, c.buffers + bn.rvar, c.nbt ? c.nbt + bn.nbt : nullptr, mean, invstd, scale,
-                                 shift, c.stream);
-  return wsl_bn_eval_affine(c.params + bn.gamma, c.params + bn.beta, c.buffers + bn.rmean, c.buffers + bn.rvar, kEps, P.F, scale, shift,
-                            c.stream);
+static int bn_fwd(const PCtx& c, const BnRef& bn, int nblk, float* mean, float* invstd, float* scale, float* shift) {
+  return wsl::bn_fwd(c.training, c.ws + c.P.stat_part, c.ws + c.P.stat_cnt, nblk, bn, c.params, c.buffers, c.nbt, mean, invstd, scale, shift,
+                c.stream);
 }
 
 static int pnet_fwd(const PCtx& c, const float* x, const float* const* cmasks, float* logits) {
@@ -238,7 +184,7 @@ static int pnet_fwd(const PCtx& c, const float* x, const float* const* cmasks, f
   }
   const float* cm1 = c.training && cmasks ? cmasks[0] : nullptr;
   const float* cm2 = c.training && cmasks ? cmasks[1] : nullptr;
-  const WslSrc cat = act_src(c.ws + P.cat, 5 * F, 5 * F * HW, c.ws + P.st2 + 10 * F, c.ws + P.st2 + 15 * F, nullptr);
+  const WslSrc cat = act_src(c.ws + P.cat, 5 * F, 5 * F * HW, c.ws + P.st2 + 10 * F, c.ws + P.st2 + 15 * F, nullptr, 1.f, nullptr);
   WSL_TRY(wsl_conv2d_fwd(&cat, nullptr, c.params + P.cb1.w, c.params + P.cb1.b, c.ws + P.zc1, 5 * F * HW, N, H, W, 5 * F, 1, 0, nullptr,
                          nullptr, c.stream));
   const WslSrc a1 = leaky_src(c, P.zc1, 5 * F, nullptr);
@@ -252,32 +198,16 @@ static int pnet_fwd(const PCtx& c, const float* x, const float* const* cmasks, f
                         0, nullptr, nullptr, c.stream);
 }
 
-static int wgrad_layer(const PCtx& c, const WslSrc* a, const float* dy, int64_t dy_bs, const PConv& cv, int dil) {
+static int wgrad_layer(const PCtx& c, const WslSrc* a, const float* dy, int64_t dy_bs, const ConvRef& cv, int dil) {
   const PPlan& P = c.P;
   const int N = P.d.N, H = P.d.H, W = P.d.W;
-  PWgBatch* wb = c.wb;
   const size_t need = ((dil > 0 ? wsl_conv2d_dil_wgrad_ws_bytes(N, H, W, cv.Ci, cv.Co, 3, dil)
                                 : wsl_conv2d_wgrad_ws_bytes(N, H, W, cv.Ci, cv.Co, cv.ks)) + 255) & ~(size_t)255;
-  if (wb->n >= 16 || wb->off + need > c.wb_cap) {
-    set_error("pnet: weight-gradient batch overflow (%d pending, %zu + %zu of %zu bytes)", wb->n, wb->off, need, c.wb_cap);
-    return WSL_EWORKSPACE;
-  }
-  char* ws = reinterpret_cast<char*>(c.ws + P.wg_ws) + wb->off;
-  if (dil > 0)
-    WSL_TRY(wsl_conv2d_dil_wgrad_partial(a, nullptr, dy, dy_bs, c.grads + cv.w, c.grads + cv.b, N, H, W, cv.Co, 3, dil, ws, need,
-                                         &wb->items[wb->n], c.stream));
-  else
-    WSL_TRY(wsl_conv2d_wgrad_partial(a, nullptr, dy, dy_bs, c.grads + cv.w, c.grads + cv.b, N, H, W, cv.Co, cv.ks, ws, need,
-                                     &wb->items[wb->n], c.stream));
-  wb->n += 1, wb->off += need;
-  return WSL_OK;
-}
-static int wgrad_flush(const PCtx& c) {
-  PWgBatch* wb = c.wb;
-  if (wb->n == 0) return WSL_OK;
-  const int rc = wsl_wgrad_reduce_batch(wb->items, wb->n, c.stream);
-  wb->n = 0, wb->off = 0;
-  return rc;
+  float *dw = c.grads + cv.w, *db = c.grads + cv.b;
+  return wgrad_push(c.wb, "pnet", c.ws + P.wg_ws, need, [&](void* ws, size_t n, WslWgradPending* q) {
+    return dil > 0 ? wsl_conv2d_dil_wgrad_partial(a, nullptr, dy, dy_bs, dw, db, N, H, W, cv.Co, 3, dil, ws, n, q, c.stream)
+                   : wsl_conv2d_wgrad_partial(a, nullptr, dy, dy_bs, dw, db, N, H, W, cv.Co, cv.ks, ws, n, q, c.stream);
+  });
 }
 
 static int leaky_bwd(const PCtx& c, float* g, size_t z, const float* cmask, int C) {
@@ -287,7 +217,7 @@ static int leaky_bwd(const PCtx& c, float* g, size_t z, const float* cmask, int 
 }
 
 // 1x1 data gradient: g [N,Ci,H,W] = conv1x1^T(dy)
-static int dgrad_1x1(const PCtx& c, const float* dy, const PConv& cv, float* g) {
+static int dgrad_1x1(const PCtx& c, const float* dy, const ConvRef& cv, float* g) {
   const PPlan& P = c.P;
   const WslSrc s = raw_src(dy, cv.Co, (int64_t)cv.Co * P.HW);
   return wsl_conv2d_fwd(&s, nullptr, c.params + cv.w, nullptr, g, (int64_t)cv.Ci * P.HW, P.d.N, P.d.H, P.d.W, cv.Ci, 1, 1, nullptr,
@@ -319,10 +249,10 @@ static int tail_bwd(const PCtx& c, const float* const* cmasks, const float* dlog
   WSL_TRY(dgrad_1x1(c, Bf, P.cb2, A));
   WSL_TRY(leaky_bwd(c, A, P.zc1, nullptr, 5 * F));
   // catblock.conv1: its data gradient is d(cat) for all five blocks at once
-  const WslSrc cat = act_src(c.ws + P.cat, 5 * F, 5 * F * HW, c.ws + P.st2 + 10 * F, c.ws + P.st2 + 15 * F, nullptr);
+  const WslSrc cat = act_src(c.ws + P.cat, 5 * F, 5 * F * HW, c.ws + P.st2 + 10 * F, c.ws + P.st2 + 15 * F, nullptr, 1.f, nullptr);
   WSL_TRY(wgrad_layer(c, &cat, A, 5 * F * HW, P.cb1, 0));
   WSL_TRY(dgrad_1x1(c, A, P.cb1, Bf));
-  return wgrad_flush(c);
+  return wgrad_flush(c.wb, c.stream);
 }
 
 // the five blocks, last first; d(cat) in bufB (left by tail_bwd), scratch in bufA
@@ -363,52 +293,22 @@ static int blocks_bwd(const PCtx& c, const float* x) {
                                  c.stream));
     }
   }
-  return wgrad_flush(c);
-}
-
-void entry_set(WslNetEntry* e, const char* name, int kind, int ndim, int64_t s0, int64_t s1, int64_t s2, int64_t s3, int64_t off) {
-  memset(e, 0, sizeof(*e));
-  snprintf(e->name, sizeof(e->name), "%s", name);
-  e->kind = kind, e->ndim = ndim, e->offset = off;
-  e->shape[0] = s0, e->shape[1] = s1, e->shape[2] = s2, e->shape[3] = s3;
+  return wgrad_flush(c.wb, c.stream);
 }
 
 // state_dict order of the reference module: block{k}.conv1, conv2, in1, in2 (BatchNorm: weight, bias, running_mean, running_var,
 // num_batches_tracked), catblock.conv1, conv2, out.conv1, conv2
 int enumerate_entries(const PPlan& P, int want, WslNetEntry* out) {
-  int idx = 0;
-  char nm[128];
-  auto conv = [&](const char* pre, const PConv& c) {
-    snprintf(nm, sizeof(nm), "%s.weight", pre);
-    if (idx++ == want) entry_set(out, nm, 0, 4, c.Co, c.Ci, c.ks, c.ks, c.w);
-    snprintf(nm, sizeof(nm), "%s.bias", pre);
-    if (idx++ == want) entry_set(out, nm, 0, 1, c.Co, 0, 0, 0, c.b);
-  };
-  auto bn = [&](const char* pre, const PBn& b) {
-    const char* f[5] = {"weight", "bias", "running_mean", "running_var", "num_batches_tracked"};
-    const int64_t off[5] = {b.gamma, b.beta, b.rmean, b.rvar, b.nbt};
-    const int kind[5] = {0, 0, 1, 1, 2};
-    for (int k = 0; k < 5; ++k) {
-      snprintf(nm, sizeof(nm), "%s.%s", pre, f[k]);
-      if (idx++ == want) entry_set(out, nm, kind[k], k == 4 ? 0 : 1, k == 4 ? 0 : P.F, 0, 0, 0, off[k]);
-    }
-  };
-  char pre[96];
+  EntryWalk e{want, out};
+  char pre[32];
   for (int k = 0; k < 5; ++k) {
-    snprintf(pre, sizeof(pre), "block%d.conv1", k + 1);
-    conv(pre, P.blk[k].c1);
-    snprintf(pre, sizeof(pre), "block%d.conv2", k + 1);
-    conv(pre, P.blk[k].c2);
-    snprintf(pre, sizeof(pre), "block%d.in1", k + 1);
-    bn(pre, P.blk[k].b1);
-    snprintf(pre, sizeof(pre), "block%d.in2", k + 1);
-    bn(pre, P.blk[k].b2);
+    const PBlock& b = P.blk[k];
+    snprintf(pre, sizeof(pre), "block%d", k + 1);
+    e.conv(pre, ".conv1", b.c1), e.conv(pre, ".conv2", b.c2), e.bn(pre, ".in1", b.b1), e.bn(pre, ".in2", b.b2);
   }
-  conv("catblock.conv1", P.cb1);
-  conv("catblock.conv2", P.cb2);
-  conv("out.conv1", P.o1);
-  conv("out.conv2", P.o2);
-  return idx;
+  e.conv("catblock", ".conv1", P.cb1), e.conv("catblock", ".conv2", P.cb2);
+  e.conv("out", ".conv1", P.o1), e.conv("out", ".conv2", P.o2);
+  return e.idx;
 }
 
 }  // namespace
@@ -451,11 +351,8 @@ extern "C" int wsl_pnet_forward(const WslPNetDesc* d, const float* params, float
   PPlan P;
   WSL_TRY(make_plan(d, P));
   WSL_REQUIRE(params && buffers && x && logits && ws, "pnet_forward: null argument");
-  if (ws_bytes < P.total_floats * sizeof(float)) {
-    set_error("pnet_forward: workspace %zu < %zu", ws_bytes, P.total_floats * sizeof(float));
-    return WSL_EWORKSPACE;
-  }
-  PCtx c{P, params, buffers, nbt, nullptr, static_cast<float*>(ws), stream, training, nullptr, 0};
+  WSL_TRY(check_ws("pnet_forward", ws_bytes, P.total_floats * sizeof(float)));
+  PCtx c{P, params, buffers, nbt, nullptr, static_cast<float*>(ws), stream, training, nullptr};
   return pnet_fwd(c, x, cmasks, logits);
 }
 
@@ -466,13 +363,10 @@ extern "C" int wsl_pnet_backward(const WslPNetDesc* d, const float* params, cons
   WSL_REQUIRE(params && x && grads && ws, "pnet_backward: null argument");
   WSL_REQUIRE(phase >= 0 && phase <= 2, "pnet_backward: phase %d", phase);
   WSL_REQUIRE(phase == 2 || dlogits, "pnet_backward: missing dlogits");
-  if (ws_bytes < P.total_floats * sizeof(float)) {
-    set_error("pnet_backward: workspace %zu < %zu", ws_bytes, P.total_floats * sizeof(float));
-    return WSL_EWORKSPACE;
-  }
-  PWgBatch wb;
-  PCtx c{P, params, nullptr, nullptr, grads, static_cast<float*>(ws), stream, 1, &wb, P.total_floats * sizeof(float)};
-  c.wb_cap = (P.wg_bytes[0] > P.wg_bytes[1] ? P.wg_bytes[0] : P.wg_bytes[1]) + 256;
+  WSL_TRY(check_ws("pnet_backward", ws_bytes, P.total_floats * sizeof(float)));
+  WgBatch wb;
+  wb.cap = (P.wg_bytes[0] > P.wg_bytes[1] ? P.wg_bytes[0] : P.wg_bytes[1]) + 256;
+  PCtx c{P, params, nullptr, nullptr, grads, static_cast<float*>(ws), stream, 1, &wb};
   if (phase == 0 || phase == 1) WSL_TRY(tail_bwd(c, cmasks, dlogits));
   if (phase == 0 || phase == 2) WSL_TRY(blocks_bwd(c, x));
   return WSL_OK;

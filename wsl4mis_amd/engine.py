@@ -167,13 +167,11 @@ class TrainEngine:
         zt, self._zt = self._zt, None
         return zt
 
-    def _regularised_losses(self, x, label_u8, z, t):
+    def _regularised_losses(self, x, label_u8, z, t, lws, nl):
         """pCE + weight * R(softmax(z)) with R = tv_loss([1:]) | MumfordShah(image, .) | entropy_loss(., C), and the dense-label
         0.5 * (CE + DiceLoss) of the fully-supervised / random-walker scripts."""
         N, H, W = x.shape[0], x.shape[2], x.shape[3]
         HW, C_ = H * W, self.model.class_num
-        nl = rt.L().wsl_loss_ws_bytes(N, C_, HW)
-        lws = rt.workspace("loss", nl)
         lo, w = self.loss_out, self.REG_WEIGHT[self.loss_kind]
         if self.loss_kind in self.FUSED_REG and self.fused_heads:
             # one call: the head's first pass keeps softmax(z), the regulariser turns it into its weighted gradient, the head's second
@@ -204,15 +202,13 @@ class TrainEngine:
         rt.call("wsl_softmax_bwd", rt.ptr(t["s"]), rt.ptr(t["ds"]), rt.ptr(t["dzx"]), N, C_, HW, rt.stream())
         rt.call("wsl_axpy", rt.ptr(t["dz1"]), rt.ptr(t["dzx"]), 1.0, N * C_ * HW, rt.stream())
 
-    def _ustm_losses(self, x, label_u8, z, t, noise):
+    def _ustm_losses(self, x, label_u8, z, t, noise, lws, nl):
         """train_weakly_supervised_ustm_2D.py:119-157: pCE + w(t) * uncertainty-masked consistency.  `noise`: None (drawn
         like the script) or a list of T//2 + 1 tensors (teacher input noise, then the T//2 double-batch noises)."""
         m, N, H, W = self.model, x.shape[0], x.shape[2], x.shape[3]
         HW, C_, T_ = H * W, self.model.class_num, 8
         if H != W:
             raise _lib.WslError("ustm rotates the batch by multiples of 90 degrees: square inputs only")
-        nl = rt.L().wsl_loss_ws_bytes(N, C_, HW)
-        lws = rt.workspace("loss", nl)
         lo = self.loss_out
         rt.call("wsl_head_fwd_bwd", rt.ptr(z), None, rt.ptr(label_u8), self.ignore, 0.0, 0.0, 1.0, rt.ptr(lo), None,
                 rt.ptr(t["dz1"]), None, N, C_, HW, rt.ptr(lws), nl, rt.stream())
@@ -237,13 +233,11 @@ class TrainEngine:
         rt.call("wsl_rot90", rt.ptr(t["dzx"]), rt.ptr(t["zr"]), N * C_, H, W, 4 - k, rt.stream())    # gradient back through rot90
         rt.call("wsl_axpy", rt.ptr(t["dz1"]), rt.ptr(t["zr"]), 1.0, N * C_ * HW, rt.stream())
 
-    def _mean_teacher_losses(self, x, label_u8, z, t, noise):
+    def _mean_teacher_losses(self, x, label_u8, z, t, noise, lws, nl):
         """dz of pCE + tv + consistency for the student logits z; teacher logits from x + noise (no gradient)."""
         m, N, H, W = self.model, x.shape[0], x.shape[2], x.shape[3]
         HW, C_ = H * W, self.model.class_num
         zt = self._teacher_logits(x, noise)                # usually already in flight on the side stream
-        nl = rt.L().wsl_loss_ws_bytes(N, C_, HW)
-        lws = rt.workspace("loss", nl)
         lo = self.loss_out
         from .utils.ramps import sigmoid_rampup
         self._cons_w = self.cons_max * sigmoid_rampup(self.it // 300, 200.0)
@@ -274,32 +268,24 @@ class TrainEngine:
             self._start_teacher(x, noise)
         outs = m._run_forward(x, keep_for_backward=True)
         z1, z2 = outs[0], (outs[1] if self.dual else None)
-        L = rt.L()
-        nl = L.wsl_loss_ws_bytes(N, m.class_num, HW)
-        lws = rt.workspace("loss", nl)
+        nl = rt.L().wsl_loss_ws_bytes(N, m.class_num, HW)
+        lws = rt.workspace("loss", nl)      # the one loss workspace of the step: every composition below gets it passed down
         if self.loss_kind == "mean_teacher":
-            self._mean_teacher_losses(x, label_u8, z1, t, noise)
-            self._finish_backward(x, t)
-            return
-        if self.loss_kind == "ustm":
-            self._ustm_losses(x, label_u8, z1, t, noise)
-            self._finish_backward(x, t)
-            return
-        if self.loss_kind in self.REGULARISED:
-            self._regularised_losses(x, label_u8, z1, t)
-            self._finish_backward(x, t)
-            return
-        if self.loss_kind == "pce_gatedcrf":              # pCE + crf_weight * GatedCRF(y): one fused entry point
+            self._mean_teacher_losses(x, label_u8, z1, t, noise, lws, nl)
+        elif self.loss_kind == "ustm":
+            self._ustm_losses(x, label_u8, z1, t, noise, lws, nl)
+        elif self.loss_kind in self.REGULARISED:
+            self._regularised_losses(x, label_u8, z1, t, lws, nl)
+        elif self.loss_kind == "pce_gatedcrf":            # pCE + crf_weight * GatedCRF(y): one fused entry point
             d = self.crf_desc
             rt.call("wsl_head_gatedcrf_fwd_bwd", rt.ptr(z1), rt.ptr(z2), rt.ptr(label_u8), self.ignore, float(beta), rt.ptr(x),
                     self.crf_radius, d["xy"], d["rgb"], d["weight"], self.crf_weight, rt.ptr(self.loss_out), rt.ptr(t["dz1"]),
                     rt.ptr(t["dz2"]), rt.ptr(t["y"]), rt.ptr(t["msg"]), N, m.class_num, H, W, rt.ptr(lws), nl, rt.stream())
-            self._finish_backward(x, t)
-            return
-        w_pse = self.w_pse if self.loss_kind == "ours_proposed" else 0.0
-        rt.call("wsl_head_fwd_bwd", rt.ptr(z1), rt.ptr(z2), rt.ptr(label_u8), self.ignore, float(beta), w_pse, 1.0,
-                rt.ptr(self.loss_out), None, rt.ptr(t["dz1"]), rt.ptr(t["dz2"]), N, m.class_num, HW, rt.ptr(lws), nl,
-                rt.stream())
+        else:
+            w_pse = self.w_pse if self.loss_kind == "ours_proposed" else 0.0
+            rt.call("wsl_head_fwd_bwd", rt.ptr(z1), rt.ptr(z2), rt.ptr(label_u8), self.ignore, float(beta), w_pse, 1.0,
+                    rt.ptr(self.loss_out), None, rt.ptr(t["dz1"]), rt.ptr(t["dz2"]), N, m.class_num, HW, rt.ptr(lws), nl,
+                    rt.stream())
         self._finish_backward(x, t)
 
     def _finish_backward(self, x, t):

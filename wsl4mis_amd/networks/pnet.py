@@ -7,25 +7,24 @@ arenas, and a forward is one autograd node that enqueues the whole kernel sequen
 dilated 3x3 convolutions of the blocks, BatchNorm, the free concat, the 1x1 head.  fp32 only.
 """
 import ctypes as C
-import math
 
 import torch
-import torch.nn as nn
 
 from .. import _lib
 from .. import runtime as rt
-from .unet import _HipUNet
+from ._arena import ArenaNet, c_layout
 
 _P_DROP = 0.3   # OutPutBlock's two nn.Dropout2d(0.3)
 
 
-class PNet2D(_HipUNet):
+class PNet2D(ArenaNet):
     """ref: networks/pnet.py PNet2D(in_chns, out_chns, num_filters, ratios) -> logits [N, out_chns, H, W]; any H x W."""
     _n_dec = 1
     PRECISIONS = {"f32": 0}
+    _NORM = ("in1", "in2")
 
     def __init__(self, in_chns, out_chns, num_filters, ratios, conv_precision="f32"):
-        nn.Module.__init__(self)
+        super().__init__()
         if conv_precision not in self.PRECISIONS:
             raise NotImplementedError(f"conv_precision {conv_precision!r}: PNet2D is built for fp32 only")
         ratios = [int(r) for r in ratios]
@@ -34,57 +33,12 @@ class PNet2D(_HipUNet):
         self.in_chns, self.out_chns, self.num_filters, self.ratios = int(in_chns), int(out_chns), int(num_filters), ratios
         self.class_num = self.out_chns
         self.conv_precision = conv_precision
-        dev = rt.device()
         d0 = self._desc(1, 16, 16)
-        L = rt.L()
-        n_ent = L.wsl_pnet_num_entries(C.byref(d0))
-        if n_ent <= 0:
-            raise _lib.WslError(L.wsl_last_error().decode())
-        self._entries = []
-        for i in range(n_ent):
-            e = _lib.WslNetEntry()
-            rt.call("wsl_pnet_entry", C.byref(d0), i, C.byref(e))
-            self._entries.append((e.name.decode(), e.kind, tuple(e.shape[k] for k in range(e.ndim)), e.offset))
-        self.n_param = L.wsl_pnet_param_count(C.byref(d0))
-        self.n_enc_param = L.wsl_pnet_block_param_count(C.byref(d0))   # the blocks: the head of the arena (data-parallel buckets)
-        n_buf = L.wsl_pnet_buffer_count(C.byref(d0))
-        n_bn = sum(1 for e in self._entries if e[1] == 2)
-        self._param_arena = torch.zeros(self.n_param + 64, dtype=torch.float32, device=dev)
-        self._grad_arena = torch.zeros(self.n_param + 64, dtype=torch.float32, device=dev)
-        self._buf_arena = torch.zeros(n_buf + 64, dtype=torch.float32, device=dev)
-        self._nbt = torch.zeros(n_bn, dtype=torch.int64, device=dev)
-        self._build_tree()
-        self._default_init()
-        self._fwd_token = 0
-        self._forced_masks = None
-        self._last_masks = None
-        self._mask_bufs = {}
+        self._build_arenas(*c_layout("wsl_pnet", d0))
+        self.n_enc_param = rt.L().wsl_pnet_block_param_count(C.byref(d0))   # the blocks: the head of the arena (data-parallel buckets)
 
     def _desc(self, N, H, W):
         return _lib.WslPNetDesc(self.in_chns, self.out_chns, self.num_filters, (C.c_int32 * 5)(*self.ratios), N, H, W)
-
-    @torch.no_grad()
-    def _default_init(self):
-        """nn.Conv2d / nn.BatchNorm2d defaults drawn from torch's global CPU generator in the reference's construction order
-        (PNetBlock builds conv1, conv2, in1, in2; BatchNorm draws nothing), so `torch.manual_seed(s); PNet2D(...)` reproduces the
-        reference's initial weights bit for bit."""
-        fan_in = 1
-        for name, kind, shape, off in self._entries:
-            n = int(math.prod(shape)) if shape else 1
-            module = name.split(".")[-2]
-            if kind == 0 and len(shape) == 4:
-                w = torch.empty(shape)
-                nn.init.kaiming_uniform_(w, a=math.sqrt(5))
-                self._param_arena[off:off + n].copy_(w.view(-1))
-                fan_in = shape[1] * shape[2] * shape[3]
-            elif kind == 0 and module in ("in1", "in2"):
-                self._param_arena[off:off + n].fill_(1.0 if name.endswith("weight") else 0.0)
-            elif kind == 0:
-                bound = 1 / math.sqrt(fan_in)
-                self._param_arena[off:off + n].copy_(torch.empty(shape).uniform_(-bound, bound))
-            elif kind == 1:
-                self._buf_arena[off:off + n].fill_(1.0 if name.endswith("running_var") else 0.0)
-        self._nbt.zero_()
 
     # ------------------------------------------------------------------ Dropout2d masks
     def set_dropout_masks(self, cmasks):
@@ -101,13 +55,9 @@ class PNet2D(_HipUNet):
         if self._forced_masks is not None:
             return list(self._forced_masks)
         dev = self._param_arena.device
-        key = (N, H, W)
-        bufs = self._mask_bufs.get(slot)
-        if bufs is None or bufs[0] != key:
-            F = self.num_filters
-            bufs = (key, [torch.empty((N, 2 * F), dtype=torch.float32, device=dev), torch.empty((N, F), dtype=torch.float32, device=dev)])
-            self._mask_bufs[slot] = bufs
-        outs = bufs[1]
+        F = self.num_filters
+        outs, = self._mask_slot(slot, (N, H, W), lambda: (
+            [torch.empty((N, 2 * F), dtype=torch.float32, device=dev), torch.empty((N, F), dtype=torch.float32, device=dev)],))
         seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
         keep = 1.0 - _P_DROP
         rt.call("wsl_draw_masks", 2, rt.ptr_array(outs), (C.c_int64 * 2)(*[t.numel() for t in outs]), (C.c_float * 2)(keep, keep),
@@ -134,8 +84,7 @@ class PNet2D(_HipUNet):
                 rt.ptr_array(cm), int(training), rt.ptr(logits), rt.ptr(ws), nws, rt.stream())
         self._last_masks = cm
         if grad_mode:
-            self._fwd_token += 1
-            self._saved = (d, ws, nws, cm)
+            self._keep(d, ws, nws, cm)
         return (logits,)
 
     def _run_backward(self, x, gouts, phase=0):
@@ -144,5 +93,5 @@ class PNet2D(_HipUNet):
             torch.zeros((d.N, self.out_chns, d.H, d.W), dtype=torch.float32, device=x.device)
         rt.call("wsl_pnet_backward", C.byref(d), rt.ptr(self._param_arena), rt.ptr(x), rt.ptr_array(cm), rt.ptr(g),
                 rt.ptr(self._grad_arena), rt.ptr(ws), nws, phase, rt.stream())
-        ga = self._grad_arena
-        return tuple(ga[off:off + n].view(shape) for _, off, n, shape in self._plist)
+        return self._grad_views()
+

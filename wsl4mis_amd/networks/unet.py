@@ -4,45 +4,24 @@ Same constructor arguments, same forward return ((N,C,H,W) logits, or a pair for
 shapes / order (202 entries for unet_cct) and parameters() order, so reference checkpoints load both ways and
 `optim.SGD(model.parameters())`, `loss.backward()`, `model.train()/eval()` work unchanged.
 
-MI355X-first differences of form: all parameters are views into ONE flat fp32 arena (so the optimiser and the RCCL
-all-reduce see a single buffer), buffers likewise, and a forward is ONE autograd node that enqueues the whole HIP
-kernel sequence through the C ABI (wsl_net_forward / wsl_net_backward) instead of ~150 ATen ops.
+MI355X-first differences of form: all parameters are views into ONE flat fp32 arena (networks/_arena.py), buffers
+likewise, and a forward is ONE autograd node that enqueues the whole HIP kernel sequence through the C ABI
+(wsl_net_forward / wsl_net_backward) instead of ~150 ATen ops.
 """
 import ctypes as C
 import math
 
 import torch
-import torch.nn as nn
 
 from .. import _lib
 from .. import runtime as rt
+from ._arena import ArenaModule, ArenaNet, c_layout
 
 _FT = (16, 32, 64, 128, 256)
 _DROP = (0.05, 0.1, 0.2, 0.3, 0.5)
 
 
-class _NetFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, mod, x, *params):
-        x = rt.f32c(x, "input")     # the kernels address x as dense NCHW: keep the tensor the forward actually read (ADVICE r2)
-        outs = mod._run_forward(x, keep_for_backward=True)
-        ctx.mod, ctx.x, ctx.token = mod, x, mod._fwd_token
-        return outs if len(outs) > 1 else outs[0]
-
-    @staticmethod
-    def backward(ctx, *gouts):
-        mod = ctx.mod
-        if ctx.token != mod._fwd_token:
-            raise _lib.WslError("backward() after a newer training forward of the same module: the activations kept "
-                                "in the module's workspace were overwritten (use a second model instance)")
-        mod._run_backward(ctx.x, gouts)
-        # autograd keeps what is returned here as p.grad and later ACCUMULATES into it in place: hand out views of a private
-        # copy, never of the arena the next wsl_net_backward overwrites (the fused TrainEngine reads the arena directly)
-        flat = mod._grad_arena.clone()
-        return (None, None) + tuple(flat[off:off + n].view(shape) for _, off, n, shape in mod._plist)
-
-
-class _HipUNet(nn.Module):
+class _HipUNet(ArenaNet):
     _n_dec = 1
     PRECISIONS = {"f32": 0, "split_f16x3": 1}
 
@@ -54,91 +33,13 @@ class _HipUNet(nn.Module):
         if conv_precision not in self.PRECISIONS:
             raise ValueError(f"conv_precision {conv_precision!r}: one of {sorted(self.PRECISIONS)}")
         self.conv_precision = conv_precision
-        dev = rt.device()
         d0 = self._desc(1, 16, 16)
-        L = rt.L()
-        n_ent = L.wsl_net_num_entries(C.byref(d0))
-        if n_ent <= 0:
-            raise _lib.WslError(L.wsl_last_error().decode())
-        self._entries = []
-        for i in range(n_ent):
-            e = _lib.WslNetEntry()
-            rt.call("wsl_net_entry", C.byref(d0), i, C.byref(e))
-            self._entries.append((e.name.decode(), e.kind, tuple(e.shape[k] for k in range(e.ndim)), e.offset))
-        self.n_param = L.wsl_net_param_count(C.byref(d0))
-        self.n_enc_param = L.wsl_net_encoder_param_count(C.byref(d0))
-        n_buf = L.wsl_net_buffer_count(C.byref(d0))
-        n_bn = sum(1 for e in self._entries if e[1] == 2)
-        # flat arenas (device memory); 64-float padding keeps float4 paths legal for any tail
-        self._param_arena = torch.zeros(self.n_param + 64, dtype=torch.float32, device=dev)
-        self._grad_arena = torch.zeros(self.n_param + 64, dtype=torch.float32, device=dev)
-        self._buf_arena = torch.zeros(n_buf + 64, dtype=torch.float32, device=dev)
-        self._nbt = torch.zeros(n_bn, dtype=torch.int64, device=dev)
-        self._build_tree()
-        self._default_init()
-        self._fwd_token = 0
-        self._forced_masks = None
-        self._last_masks = None
-        self._mask_bufs = {}
+        self._build_arenas(*c_layout("wsl_net", d0))
+        self.n_enc_param = rt.L().wsl_net_encoder_param_count(C.byref(d0))
 
     # ------------------------------------------------------------------ structure
     def _desc(self, N, H, W):
         return _lib.WslNetDesc(self.in_chns, self.class_num, self._n_dec, N, H, W, self.PRECISIONS[self.conv_precision], 0)
-
-    def _build_tree(self):
-        """Container modules named after the reference's attribute path, so state_dict() keys are identical."""
-        self._plist = []
-        for name, kind, shape, off in self._entries:
-            *path, leaf = name.split(".")
-            m = self
-            for part in path:
-                if part not in m._modules:
-                    m.add_module(part, nn.Module())
-                m = m._modules[part]
-            n = int(math.prod(shape)) if shape else 1
-            if kind == 0:
-                p = nn.Parameter(self._param_arena[off:off + n].view(shape))
-                m.register_parameter(leaf, p)
-                self._plist.append((p, off, n, shape))
-            elif kind == 1:
-                m.register_buffer(leaf, self._buf_arena[off:off + n].view(shape))
-            else:
-                m.register_buffer(leaf, self._nbt[off])
-
-    @torch.no_grad()
-    def _default_init(self):
-        """nn.Conv2d / nn.BatchNorm2d default initialisation drawn from torch's global CPU generator in the reference's
-        construction order, so `torch.manual_seed(s); net_factory(...)` reproduces the reference's initial weights bit
-        for bit (ref: net_factory.py:9-10 builds the module on the CPU, then .cuda())."""
-        for name, kind, shape, off in self._entries:
-            n = int(math.prod(shape)) if shape else 1
-            if kind == 0 and len(shape) == 4:
-                w = torch.empty(shape)
-                nn.init.kaiming_uniform_(w, a=math.sqrt(5))
-                self._param_arena[off:off + n].copy_(w.view(-1))
-                self._pending_fan_in = shape[1] * shape[2] * shape[3]
-            elif kind == 0:
-                parts = name.split(".")
-                is_bn = parts[-2] in ("1", "5")
-                if is_bn:
-                    self._param_arena[off:off + n].fill_(1.0 if parts[-1] == "weight" else 0.0)
-                else:
-                    bound = 1 / math.sqrt(self._pending_fan_in)
-                    self._param_arena[off:off + n].copy_(torch.empty(shape).uniform_(-bound, bound))
-            elif kind == 1:
-                self._buf_arena[off:off + n].fill_(1.0 if name.endswith("running_var") else 0.0)
-        self._nbt.zero_()
-
-    def _ensure_arena(self):
-        """Re-attach parameters that were re-allocated behind our back (model.to(...), p.data = ...)."""
-        base = self._param_arena.data_ptr()
-        for p, off, n, shape in self._plist:
-            if p.data_ptr() != base + 4 * off:
-                if p.device != self._param_arena.device or p.dtype != torch.float32:
-                    raise _lib.WslError("model parameters were moved off the GPU / cast away from float32")
-                with torch.no_grad():
-                    self._param_arena[off:off + n].copy_(p.data.reshape(-1))
-                    p.data = self._param_arena[off:off + n].view(shape)
 
     # ------------------------------------------------------------------ masks (host-side RNG = torch's, on the device)
     def set_dropout_masks(self, emasks, cmasks=None):
@@ -146,8 +47,6 @@ class _HipUNet(nn.Module):
         self._forced_masks = emasks if callable(emasks) else (None if emasks is None and cmasks is None else (emasks, cmasks))
 
     def _draw_masks(self, N, H, W, training, slot="infer"):
-        """slot: 'train' for a forward whose masks a pending backward will read again, 'infer' for every other forward --
-        two buffer sets, so a no_grad / eval forward between forward and backward cannot redraw the saved masks."""
         dev = self._param_arena.device
         if callable(self._forced_masks):                 # (tests) masks that depend on the batch shape of the forward
             em, cm = self._forced_masks(N, H, W)
@@ -158,22 +57,18 @@ class _HipUNet(nn.Module):
         want_e = training and em is None
         want_c = self._n_dec == 2 and cm is None     # F.dropout2d(x, 0.5) is active in eval mode too (unet.py:254-256,344)
         if want_e or want_c:
-            key = (N, H, W)
-            bufs = self._mask_bufs.get(slot)
-            if bufs is None or bufs[0] != key:              # persistent mask buffers, refilled in place every forward
-                bufs = (key,
-                        [torch.empty((N, _FT[l], H >> l, W >> l), dtype=torch.uint8, device=dev) for l in range(5)],
-                        [torch.empty((N, _FT[l]), dtype=torch.float32, device=dev) for l in range(5)])
-                self._mask_bufs[slot] = bufs
+            ebufs, cbufs = self._mask_slot(slot, (N, H, W), lambda: (
+                [torch.empty((N, _FT[l], H >> l, W >> l), dtype=torch.uint8, device=dev) for l in range(5)],
+                [torch.empty((N, _FT[l]), dtype=torch.float32, device=dev) for l in range(5)]))
             outs, probs, scales, isf = [], [], [], []
             if want_e:
-                em = bufs[1]
+                em = ebufs
                 outs += em
                 probs += [1.0 - p for p in _DROP]
                 scales += [1.0] * 5
                 isf += [0] * 5
             if want_c:
-                cm = bufs[2]
+                cm = cbufs
                 outs += cm
                 probs += [0.5] * 5
                 scales += [2.0] * 5
@@ -207,8 +102,7 @@ class _HipUNet(nn.Module):
                 rt.ptr(ws), nws, rt.stream())
         self._last_masks = (em, cm)
         if grad_mode:
-            self._fwd_token += 1
-            self._saved = (d, ws, nws, em, cm)
+            self._keep(d, ws, nws, em, cm)
         return (lm, la) if la is not None else (lm,)
 
     def _run_backward(self, x, gouts, phase=0):
@@ -221,28 +115,7 @@ class _HipUNet(nn.Module):
         rt.call("wsl_net_backward", C.byref(d), rt.ptr(self._param_arena), rt.ptr(x), rt.ptr_array(em), rt.ptr_array(cm),
                 rt.ptr(g[0]), rt.ptr(g[1]) if self._n_dec == 2 else None, rt.ptr(self._grad_arena), rt.ptr(ws), nws, phase,
                 rt.stream())
-        ga = self._grad_arena
-        return tuple(ga[off:off + n].view(shape) for _, off, n, shape in self._plist)
-
-    def forward(self, x):
-        if x.requires_grad:
-            raise NotImplementedError("gradient with respect to the input image is not built (no trainer of the "
-                                      "reference's hot path asks for it)")
-        if self.training and torch.is_grad_enabled():
-            return _NetFn.apply(self, x, *[p for p, _, _, _ in self._plist])
-        outs = self._run_forward(x)
-        return outs if len(outs) > 1 else outs[0]
-
-    # flat views for the fused trainer / data-parallel engine
-    def flat_params(self):
-        self._ensure_arena()
-        return self._param_arena[:self.n_param]
-
-    def flat_grads(self):
-        return self._grad_arena[:self.n_param]
-
-    def cuda(self, device=None):   # already resident; keep net_factory(...).cuda()-style call sites working
-        return self
+        return self._grad_views()
 
 
 class UNet(_HipUNet):
@@ -282,13 +155,14 @@ class _UpFn(torch.autograd.Function):
         return (None, dx1, dx2) + grads
 
 
-class UpBlock(nn.Module):
+class UpBlock(ArenaModule):
     """ref: networks/unet.py:47-68 -- `UpBlock(in_channels1, in_channels2, out_channels, dropout_p, bilinear=True)`,
     forward(x1, x2).  SURVEY 8f rank 4 (opt-in): the TRANSPOSED-CONVOLUTION branch (`bilinear=False`: ConvTranspose2d(k=2,
     s=2) -> cat([x2, x1]) -> ConvBlock) as a module of its own on the HIP kernels, with the reference's state_dict layout
     (up.weight [C1,C2,2,2], up.bias, conv.conv_conv.{0,1,4,5}.*) and default initialisation draws.  The reference's Decoder
     never selects this branch (it builds every UpBlock with the default bilinear=True -- that path lives inside UNet /
     UNet_CCT), so `bilinear=True` is not offered stand-alone."""
+    _MOVED = "UpBlock parameters were moved off the GPU / cast away from float32"
 
     def __init__(self, in_channels1, in_channels2, out_channels, dropout_p, bilinear=True):
         super().__init__()
@@ -296,80 +170,32 @@ class UpBlock(nn.Module):
             raise NotImplementedError("the bilinear UpBlock is built into UNet / UNet_CCT; stand-alone only bilinear=False is")
         self.bilinear = False
         self.c1, self.c2, self.co, self.p = int(in_channels1), int(in_channels2), int(out_channels), float(dropout_p)
-        dev = rt.device()
         n = rt.L().wsl_upblock_t_param_count(C.byref(self._desc(1, 1, 1)))
         if n <= 0:
             raise _lib.WslError(rt.L().wsl_last_error().decode())
-        self.n_param = int(n)
-        self._param_arena = torch.zeros(self.n_param + 64, dtype=torch.float32, device=dev)
-        self._grad_arena = torch.zeros(self.n_param + 64, dtype=torch.float32, device=dev)
-        self._buf_arena = torch.zeros(4 * self.co + 64, dtype=torch.float32, device=dev)
-        self._nbt = torch.zeros(2, dtype=torch.int64, device=dev)
         c1, c2, co = self.c1, self.c2, self.co
         layout = [("up.weight", (c1, c2, 2, 2)), ("up.bias", (c2,)), ("conv.conv_conv.0.weight", (co, 2 * c2, 3, 3)),
                   ("conv.conv_conv.0.bias", (co,)), ("conv.conv_conv.1.weight", (co,)), ("conv.conv_conv.1.bias", (co,)),
                   ("conv.conv_conv.4.weight", (co, co, 3, 3)), ("conv.conv_conv.4.bias", (co,)),
                   ("conv.conv_conv.5.weight", (co,)), ("conv.conv_conv.5.bias", (co,))]
-        self._plist, off = [], 0
+        entries, off = [], 0
         for name, shape in layout:
-            *path, leaf = name.split(".")
-            m = self
-            for part in path:
-                if part not in m._modules:
-                    m.add_module(part, nn.Module())
-                m = m._modules[part]
-            k = int(math.prod(shape))
-            prm = nn.Parameter(self._param_arena[off:off + k].view(shape))
-            m.register_parameter(leaf, prm)
-            self._plist.append((prm, off, k, shape))
-            if leaf == "bias" and path[-1] in ("1", "5"):           # BatchNorm: its buffers follow its parameters
-                bi = 0 if path[-1] == "1" else 1
-                m.register_buffer("running_mean", self._buf_arena[2 * bi * co:(2 * bi + 1) * co])
-                m.register_buffer("running_var", self._buf_arena[(2 * bi + 1) * co:(2 * bi + 2) * co])
-                m.register_buffer("num_batches_tracked", self._nbt[bi])
-            off += k
-        assert off == self.n_param
-        self._default_init()
-        self._fwd_token, self._forced_mask, self._saved = 0, None, None
+            entries.append((name, 0, shape, off))
+            off += math.prod(shape)
+            mod, leaf = name.rsplit(".", 1)
+            if leaf == "bias" and self.is_norm(name):               # BatchNorm: its buffers follow its parameters
+                bi = 0 if mod.endswith("1") else 1
+                entries += [(mod + ".running_mean", 1, (co,), 2 * bi * co), (mod + ".running_var", 1, (co,), (2 * bi + 1) * co),
+                            (mod + ".num_batches_tracked", 2, (), bi)]
+        assert off == n
+        self._build_arenas(entries, n, 4 * co)
 
     def _desc(self, N, h, w):
         return _lib.WslUpBlockDesc(self.c1, self.c2, self.co, N, h, w, self.p)
 
-    @torch.no_grad()
-    def _default_init(self):
-        """the reference's construction-order draws: ConvTranspose2d (kaiming_uniform(a=sqrt(5)) with fan_in = C2 * 4 -- torch
-        takes dim 1 of the [C1,C2,2,2] weight --, bias U(+-1/sqrt(fan_in))), then the ConvBlock's Conv2d / BatchNorm2d"""
-        for prm, off, k, shape in self._plist:
-            name = [n for n, q in self.named_parameters() if q is prm][0]
-            if len(shape) == 4:
-                w = torch.empty(shape)
-                nn.init.kaiming_uniform_(w, a=math.sqrt(5))
-                prm.copy_(w)
-                fan_in = shape[1] * shape[2] * shape[3]
-            elif name.split(".")[-2] in ("1", "5"):
-                prm.fill_(1.0 if name.endswith("weight") else 0.0)
-            else:
-                bound = 1 / math.sqrt(fan_in)
-                prm.copy_(torch.empty(shape).uniform_(-bound, bound))
-        self._buf_arena.zero_()
-        self._buf_arena[self.co:2 * self.co] = 1.0
-        self._buf_arena[3 * self.co:4 * self.co] = 1.0
-        self._nbt.zero_()
-
     def set_dropout_mask(self, emask):
         """inject the nn.Dropout keep mask [N, Co, 2h, 2w] uint8 of the next forward(s) (parity tests); None = draw"""
-        self._forced_mask = emask
-
-    def _ensure_arena(self):
-        """Re-attach parameters that were re-allocated behind the module (p.data = ..., .double().float(), ...)."""
-        base = self._param_arena.data_ptr()
-        for prm, off, k, shape in self._plist:
-            if prm.data_ptr() != base + 4 * off:
-                if prm.device != self._param_arena.device or prm.dtype != torch.float32:
-                    raise _lib.WslError("UpBlock parameters were moved off the GPU / cast away from float32")
-                with torch.no_grad():
-                    self._param_arena[off:off + k].copy_(prm.data.reshape(-1))
-                    prm.data = self._param_arena[off:off + k].view(shape)
+        self._forced_masks = emask
 
     def _run_forward(self, x1, x2, keep=False):
         x1, x2 = rt.f32c(x1, "x1"), rt.f32c(x2, "x2")
@@ -383,7 +209,7 @@ class UpBlock(nn.Module):
         training = self.training
         em = None
         if training and self.p > 0:
-            em = self._forced_mask
+            em = self._forced_masks
             if em is None:
                 em = torch.empty((N, self.co, 2 * h, 2 * w), dtype=torch.uint8, device=x1.device)
                 seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
@@ -393,8 +219,7 @@ class UpBlock(nn.Module):
         rt.call("wsl_upblock_t_forward", C.byref(d), rt.ptr(self._param_arena), rt.ptr(self._buf_arena), rt.ptr(self._nbt),
                 rt.ptr(x1), rt.ptr(x2), rt.ptr(em), int(training), rt.ptr(out), rt.ptr(ws), nws, rt.stream())
         if keep:
-            self._fwd_token += 1
-            self._saved = (d, ws, nws, em)
+            self._keep(d, ws, nws, em)
         return out
 
     def _run_backward(self, x1, x2, gout, need):
@@ -405,8 +230,7 @@ class UpBlock(nn.Module):
         dx2 = torch.empty(x2.shape, dtype=torch.float32, device=x2.device) if need[1] else None
         rt.call("wsl_upblock_t_backward", C.byref(d), rt.ptr(self._param_arena), rt.ptr(x1), rt.ptr(x2), rt.ptr(em), rt.ptr(g),
                 rt.ptr(self._grad_arena), rt.ptr(dx1), rt.ptr(dx2), rt.ptr(ws), nws, rt.stream())
-        flat = self._grad_arena.clone()
-        return dx1, dx2, tuple(flat[off:off + k].view(shape) for _, off, k, shape in self._plist)
+        return dx1, dx2, self._grad_views(private=True)
 
     def forward(self, x1, x2):
         if self.training and torch.is_grad_enabled():
