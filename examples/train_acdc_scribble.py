@@ -4,6 +4,10 @@ code/train_weakly_supervised_pCE_WSL4MIS (ours_proposed) / ..._pCE_GatedCRFLoss_
 
     BaseDataSets(h5lite) -> BatchRandomGenerator (device augmentation) -> TrainEngine.step -> val_2D metrics
 
+--loss s2l is the flow of code/train_s2l.py (Scribble2Label): BaseDataSets_s2l keeps a running prediction average per training slice,
+BatchRandomGenerator_s2l carries it through the augmentation, the engine reads it from --thr_iter on and refreshes it after every
+--period_iter steps (TrainEngine.update_ensemble).
+
     python examples/train_acdc_scribble.py --root_path <.../data/ACDC> --fold fold1 --max_iterations 60000
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/train_acdc_scribble.py ...
 
@@ -22,6 +26,7 @@ import torch.distributed as dist
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from wsl4mis_amd import val_2D  # noqa: E402
 from wsl4mis_amd.dataloaders.dataset import BaseDataSets, BatchRandomGenerator  # noqa: E402
+from wsl4mis_amd.dataloaders.dataset_s2l import BaseDataSets_s2l, BatchRandomGenerator_s2l  # noqa: E402
 from wsl4mis_amd.engine import TrainEngine  # noqa: E402
 
 
@@ -30,8 +35,16 @@ def main(argv=None):
     ap.add_argument("--root_path", required=True)
     ap.add_argument("--fold", default="fold1")
     ap.add_argument("--sup_type", default="scribble")
-    ap.add_argument("--model", default="unet_cct", choices=["unet_cct", "unet"])
-    ap.add_argument("--loss", default="ours_proposed", choices=["ours_proposed", "pce", "pce_gatedcrf", "pce_tv", "pce_ms", "pce_entropy", "ce_dice", "mean_teacher", "ustm"])
+    ap.add_argument("--model", default=None, choices=["unet_cct", "unet", "pnet"], help="default: unet_cct, and unet for --loss s2l "
+                    "(Scribble2Label trains a single-decoder net: unet or pnet)")
+    ap.add_argument("--loss", default="ours_proposed", choices=["ours_proposed", "pce", "pce_gatedcrf", "pce_tv", "pce_ms", "pce_entropy", "ce_dice", "mean_teacher", "ustm", "s2l"])
+    # Scribble2Label (train_s2l.py:62-65)
+    ap.add_argument("--period_iter", type=int, default=100)
+    ap.add_argument("--thr_iter", type=int, default=6000)
+    ap.add_argument("--thr_conf", type=float, default=0.8)
+    ap.add_argument("--alpha", type=float, default=0.2)
+    ap.add_argument("--ensemble_mode", default="reference", choices=["reference", "eval"], help="s2l: 'reference' = the reference's update "
+                    "pass (one train-mode forward per slice), 'eval' = batched eval-mode forwards (a departure: TrainEngine.update_ensemble)")
     ap.add_argument("--num_classes", type=int, default=4)
     ap.add_argument("--max_iterations", type=int, default=60000)
     ap.add_argument("--stop_iterations", type=int, default=0, help="stop after this many iterations while keeping the poly schedule "
@@ -54,6 +67,8 @@ def main(argv=None):
                     "run the SAME trajectory up to fp32 round-off: profiles/r3_acdc_short_schedule.md)")
     ap.add_argument("--resume", default=None, help="a state_dict .pth (the reference's or ours: same keys) to start from")
     args = ap.parse_args(argv)
+    if args.model is None:
+        args.model = "unet" if args.loss == "s2l" else "unet_cct"
 
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
@@ -61,14 +76,18 @@ def main(argv=None):
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group("nccl")
     random.seed(args.seed), np.random.seed(args.seed + rank), torch.manual_seed(args.seed)
-    train = BaseDataSets(base_dir=args.root_path, split="train", fold=args.fold, sup_type=args.sup_type,
-                         labeled_type=args.labeled_type, cache=True)
+    s2l = args.loss == "s2l"
+    if s2l:      # every slice of the fold's training patients, held in memory with its weight store (train_s2l.py:86-87)
+        train = BaseDataSets_s2l(base_dir=args.root_path, fold=args.fold, class_num=args.num_classes)
+    else:
+        train = BaseDataSets(base_dir=args.root_path, split="train", fold=args.fold, sup_type=args.sup_type,
+                             labeled_type=args.labeled_type, cache=True)
     val = BaseDataSets(base_dir=args.root_path, split="val", fold=args.fold, cache=True)
     if len(train) == 0:
         raise SystemExit("no training slices for this fold under " + args.root_path)
-    aug = BatchRandomGenerator(args.patch_size, device_cache=True)
+    aug = BatchRandomGenerator_s2l(args.patch_size) if s2l else BatchRandomGenerator(args.patch_size, device_cache=True)
     eng = TrainEngine(args.model, 1, args.num_classes, base_lr=args.base_lr, max_iterations=args.max_iterations,
-                      loss=args.loss)
+                      loss=args.loss, thr_iter=args.thr_iter, thr_conf=args.thr_conf, s2l_alpha=args.alpha, period_iter=args.period_iter)
     if args.resume:
         eng.model.load_state_dict(torch.load(args.resume, map_location="cpu"))
     if args.snapshot_path and rank == 0:
@@ -86,16 +105,22 @@ def main(argv=None):
             idx = perm[b:b + args.batch_size]
             if len(idx) < 2:                            # BatchNorm needs more than one slice
                 continue
-            image, label = aug([train[int(i)] for i in idx])
+            weight = None
+            if s2l:
+                image, _, label, weight = aug([train[int(i)] for i in idx])
+            else:
+                image, label = aug([train[int(i)] for i in idx])
             if args.oracle_stream:
                 from wsl4mis_amd.networks.unet import _DROP, _FT
                 n, (ph, pw) = len(idx), args.patch_size
                 em = [(torch.rand((n, _FT[l], ph >> l, pw >> l)) >= _DROP[l]).to(torch.uint8).cuda() for l in range(5)]
                 eng.model.set_dropout_masks(em, None)
-            eng.step(image, label, random.random() + 1e-10)
+            eng.step(image, label, random.random() + 1e-10, weight=weight)
             if args.oracle_stream:
                 eng.model.set_dropout_masks(None, None)
             it += 1
+            if s2l and eng.ensemble_due():              # train_s2l.py:214-243; every rank refreshes its own full store
+                eng.update_ensemble(train, mode=args.ensemble_mode, patch_size=tuple(args.patch_size))
             if rank == 0 and (it % args.log_every == 0 or it == 1):
                 o = eng.losses()
                 history.append((it, o["loss"]))

@@ -373,6 +373,55 @@ typedef struct {
 } WslAugSample;
 int wsl_augment_batch(const WslAugSample* samples, int n, float* out_img, uint8_t* out_lab, int Ho, int Wo, void* stream);
 
+/* ------------------------------------------------------------------------------------------------ Scribble2Label
+ * (ref: train_s2l.py with dataloaders/dataset_s2l.py.)  Three pieces: the loss head, the running prediction average ("ensemble")
+ * kept per training slice at native resolution, and the 4-array augmentation.  Same conventions as the loss and data entries above:
+ * no allocation, no synchronisation, order-fixed two-stage reductions (bit-reproducible).
+ *
+ * wsl_s2l_head_fwd_bwd (ref: train_s2l.py:123-147): ce = CE(z, scribble, ignore); pseudo labels u[p] = the HIGHEST class c with
+ * weight[p, c] > thr_conf (fp32 compare) where scribble[p] == ignore, else ignore; ce_u = CE(z, u, ignore); loss = ce + w_u * ce_u.
+ * Each CE is the mean over its own valid pixels (NaN when it has none -- then loss is NaN as well, like torch).
+ * out[0..4] = {loss, ce, ce_u, n_valid, n_u}.  dz = gscale * ((softmax - onehot(scribble)) / n_valid on scribble pixels,
+ * w_u * (softmax - onehot(u)) / n_u on pseudo-labelled pixels, 0 elsewhere); dz may be NULL (forward only).
+ * weight: [N, H, W, C] channels-last fp32, as the reference's loader hands it over.  u_labels: uint8 [N, H, W] or NULL.  C <= 8.
+ * One pass over logits + scribble + weight (both NLL sums, both counts, the per-pixel target byte kept in ws), a finalize, one pass
+ * that reads logits + target byte and writes dz.  ws: wsl_s2l_head_ws_bytes(). */
+size_t wsl_s2l_head_ws_bytes(int N, int C, int HW);
+int wsl_s2l_head_fwd_bwd(const float* z, const uint8_t* scribble, const float* weight, int ignore, float thr_conf, float w_u,
+                         float gscale, float* out, uint8_t* u_labels, float* dz, int N, int C, int HW, void* ws, size_t ws_bytes,
+                         void* stream);
+/* wsl_s2l_ensemble_update (ref: train_s2l.py:228-243): for slice i with logits z[i] [C, Hn, Wn] at the network size and a store
+ * slots[i].weight [h, w, C] at the slice's native size, per native pixel
+ *     pred = softmax(z[i])[:, Z_h(y), Z_w(x)]                 (scipy.ndimage.zoom(pred, (1, h / Hn, w / Wn), order=0): the same
+ *                                                              nearest-neighbour index function as wsl_augment_batch's zoom)
+ *     weight[y, x, c] = alpha * pred[c] + (1 - alpha) * weight[y, x, c]
+ * in fp32 with alpha and 1 - alpha (subtracted in double) rounded to fp32: two multiplies and an add, no FMA contraction.
+ * The slot array lives on the HOST (copied into the launch); one launch per 64 slices of any sizes. */
+typedef struct WslS2lSlot {
+  float* weight;   /* [h, w, C] */
+  int h, w;
+} WslS2lSlot;
+int wsl_s2l_ensemble_update(const float* z, const WslS2lSlot* slots, int n, int C, int Hn, int Wn, double alpha, void* stream);
+/* wsl_augment_batch_s2l (ref: dataloaders/dataset_s2l.py:103-153 RandomGenerator_s2l): the gather of wsl_augment_batch for the four
+ * arrays of a Scribble2Label sample -- image, mask (the dense label; pointer may be NULL), scribble and the weight map [h, w, C],
+ * all through the same index map.  The reference calls ndimage.rotate WITHOUT cval here, so every fill is 0 (rotated-in corners of
+ * the scribble become labelled background).  Outputs: out_img [n,1,Ho,Wo] f32, out_mask [n,Ho,Wo] u8 (NULL: not produced),
+ * out_scr [n,Ho,Wo] u8, out_weight [n,Ho,Wo,C] f32; out_scr / out_weight may be NULL as well (the update pass zooms images only).
+ * The zoom is scipy's to the last pixel: where (Ho - 1) * ((rows - 1) / (Ho - 1)) exceeds rows - 1 in double (26 -> 12, ...) the last
+ * output row is scipy's fill 0, not the edge row; wsl_s2l_ensemble_update's zoom-back does the same (pred = 0 there). */
+typedef struct {
+  const float* img;      /* [h, w] */
+  const uint8_t* mask;   /* [h, w] or NULL */
+  const uint8_t* scr;    /* [h, w] */
+  const float* weight;   /* [h, w, C] */
+  int h, w;
+  int op, k, axis;       /* as WslAugSample */
+  int _pad;
+  double m00, m01, m10, m11, off0, off1;
+} WslAugSampleS2l;
+int wsl_augment_batch_s2l(const WslAugSampleS2l* samples, int n, int C, float* out_img, uint8_t* out_mask, uint8_t* out_scr,
+                          float* out_weight, int Ho, int Wo, void* stream);
+
 /* Validation metric pieces (medpy.metric.binary.hd95 as called by code/val_2D.py:7-15): the surface of a binary [D,H,W]
  * volume (object minus its erosion by the 6-neighbourhood, background outside the array) and, for every point of one
  * voxel list ([n][3] int64 z,y,x -- torch.nonzero layout), the exact squared distance to the nearest point of another.

@@ -61,6 +61,16 @@ class WslAugSample(C.Structure):
                 ("m01", C.c_double), ("m10", C.c_double), ("m11", C.c_double), ("off0", C.c_double), ("off1", C.c_double)]
 
 
+class WslS2lSlot(C.Structure):
+    _fields_ = [("weight", c_fp), ("h", C.c_int32), ("w", C.c_int32)]
+
+
+class WslAugSampleS2l(C.Structure):
+    _fields_ = [("img", c_fp), ("mask", c_fp), ("scr", c_fp), ("weight", c_fp), ("h", C.c_int32), ("w", C.c_int32),
+                ("op", C.c_int32), ("k", C.c_int32), ("axis", C.c_int32), ("_pad", C.c_int32), ("m00", C.c_double),
+                ("m01", C.c_double), ("m10", C.c_double), ("m11", C.c_double), ("off0", C.c_double), ("off1", C.c_double)]
+
+
 i32, i64, f32, f64, sz = C.c_int, C.c_int64, C.c_float, C.c_double, C.c_size_t
 PS, PD, PE = C.POINTER(WslSrc), C.POINTER(WslNetDesc), C.POINTER(WslNetEntry)
 PP = C.POINTER(c_fp)
@@ -148,6 +158,10 @@ _PROTOS = {
     "wsl_surface_u8": (i32, [c_fp, c_fp, i32, i32, i32, c_fp]),
     "wsl_nearest_dist2": (i32, [c_fp, i32, c_fp, i32, c_fp, c_fp]),
     "wsl_augment_batch": (i32, [C.POINTER(WslAugSample), i32, c_fp, c_fp, i32, i32, c_fp]),
+    "wsl_s2l_head_ws_bytes": (sz, [i32, i32, i32]),
+    "wsl_s2l_head_fwd_bwd": (i32, [c_fp, c_fp, c_fp, i32, f32, f32, f32, c_fp, c_fp, c_fp, i32, i32, i32, c_fp, sz, c_fp]),
+    "wsl_s2l_ensemble_update": (i32, [c_fp, C.POINTER(WslS2lSlot), i32, i32, i32, i32, f64, c_fp]),
+    "wsl_augment_batch_s2l": (i32, [C.POINTER(WslAugSampleS2l), i32, i32, c_fp, c_fp, c_fp, c_fp, i32, i32, c_fp]),
     "wsl_noisy_copy": (i32, [c_fp, c_fp, c_fp, i64, i32, f32, f32, C.c_uint64, c_fp]),
     "wsl_head_gatedcrf_fwd_bwd": (i32, [c_fp, c_fp, c_fp, i32, f64, c_fp, i32, f32, f32, f32, f32, c_fp, c_fp, c_fp, c_fp, c_fp,
                                         i32, i32, i32, i32, c_fp, sz, c_fp]),

@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "wsl_rt.h"
+#include "wsl_zoom.h"
 
 namespace wsl {
 
@@ -18,27 +19,18 @@ struct AugTable {
   WslAugSample s[kAugMax];
 };
 
-#ifdef WSL_HOST_EMUL
-static inline double dmul(double a, double b) { return a * b; }   // emulator TU is built with -ffp-contract=off
-static inline double dadd(double a, double b) { return a + b; }
-#else
-__device__ __forceinline__ double dmul(double a, double b) { return __dmul_rn(a, b); }
-__device__ __forceinline__ double dadd(double a, double b) { return __dadd_rn(a, b); }
-#endif
-
 __global__ __launch_bounds__(256) void augment_kernel(AugTable t, float* out_img, uint8_t* out_lab, int Ho, int Wo) {
   const WslAugSample& s = t.s[blockIdx.y];
   const int h = s.h, w = s.w;
   // shape after step 1 (rot90 by an odd k swaps the axes)
   const bool swap = s.op == 1 && (s.k & 1);
   const int R = swap ? w : h, Cc = swap ? h : w;
-  const double sy = Ho > 1 ? (double)(R - 1) / (double)(Ho - 1) : 0.0, sx = Wo > 1 ? (double)(Cc - 1) / (double)(Wo - 1) : 0.0;
+  const double sy = zoom0_scale(R, Ho), sx = zoom0_scale(Cc, Wo);
   float* oi = out_img + (int64_t)blockIdx.y * Ho * Wo;
   uint8_t* ol = out_lab + (int64_t)blockIdx.y * Ho * Wo;
   for (int o = blockIdx.x * kThreads + threadIdx.x; o < Ho * Wo; o += gridDim.x * kThreads) {
     const int oy = o / Wo, ox = o - oy * Wo;
-    int i = (int)floor(dadd(dmul((double)oy, sy), 0.5)), j = (int)floor(dadd(dmul((double)ox, sx), 0.5));
-    i = i < 0 ? 0 : (i > R - 1 ? R - 1 : i), j = j < 0 ? 0 : (j > Cc - 1 ? Cc - 1 : j);
+    int i = zoom0_index(oy, sy, R), j = zoom0_index(ox, sx, Cc);
     int y = i, x = j;
     bool inside = true;
     if (s.op == 1) {

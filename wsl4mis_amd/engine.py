@@ -14,6 +14,9 @@ Steps reproduced (reference file:line, all under code/):
   'mean_teacher'    SURVEY 8d config 4 (unet student + EMA teacher): pCE + 1e-2*tv_loss(softmax[1:]) (pCE_TV_2D.py:113-114)
                     + w(t)*mean((softmax(s)-softmax(teacher(x+noise)))^2) (train_mean_teacher_2D.py:147-171); teacher =
                     EMA of the student every step (train_weakly_supervised_ustm_2D.py:61-65,163), kept in train mode
+  's2l'             train_s2l.py:123-147,214-243 (Scribble2Label; unet | pnet): pCE while it < thr_iter, then pCE + 0.5 * CE on the
+                    pseudo labels thresholded from the running prediction average `weight` (step(..., weight=w));
+                    update_ensemble(dataset) is that average's refresh, due after every step with it % period_iter == 0
 Optimiser: SGD(lr, momentum 0.9, wd 1e-4) with the poly schedule applied one step late (ours_proposed.py:126-132).
 
 Data parallel (DDP-equivalent semantics): one process per GPU, per-rank BatchNorm statistics and loss
@@ -44,8 +47,9 @@ class TrainEngine:
 
     def __init__(self, net_type="unet_cct", in_chns=1, class_num=4, base_lr=0.01, max_iterations=60000, momentum=0.9,
                  weight_decay=1e-4, loss="ours_proposed", w_pse=0.5, crf_radius=5, crf_weight=0.1,
-                 crf_desc=None, ignore_index=4, model=None, force_dp=False, conv_precision="f32"):
-        if loss not in ("ours_proposed", "pce", "pce_gatedcrf", "mean_teacher", "ustm") + self.REGULARISED:
+                 crf_desc=None, ignore_index=4, model=None, force_dp=False, conv_precision="f32", thr_iter=6000, thr_conf=0.8,
+                 s2l_alpha=0.2, period_iter=100):
+        if loss not in ("ours_proposed", "pce", "pce_gatedcrf", "mean_teacher", "ustm", "s2l") + self.REGULARISED:
             raise NotImplementedError(f"loss composition '{loss}'")
         # conv_precision: "f32" (default, the headline path) | "split_f16x3" (opt-in: networks/unet.py, include/wsl_hip.h)
         self.model = model if model is not None else net_factory(net_type, in_chns, class_num, conv_precision=conv_precision)
@@ -57,7 +61,12 @@ class TrainEngine:
             raise _lib.WslError("'ours_proposed' needs the dual-branch unet_cct")
         if loss in self.REGULARISED and self.dual:
             raise _lib.WslError(f"'{loss}' is a single-branch (unet) composition")
+        if loss == "s2l" and self.dual:
+            raise _lib.WslError("'s2l' is a single-decoder composition (unet, pnet)")
         self.loss_kind, self.w_pse, self.ignore = loss, w_pse, ignore_index
+        # Scribble2Label (train_s2l.py:62-65): threshold iteration / confidence, EMA weight of the store, update period; w_u: :147
+        self.thr_iter, self.thr_conf, self.s2l_alpha, self.period_iter, self.s2l_w_u = thr_iter, thr_conf, s2l_alpha, period_iter, 0.5
+        self._s2l_fused, self._patch = False, None
         self.crf_radius, self.crf_weight = crf_radius, crf_weight
         self.crf_desc = crf_desc or {"weight": 1.0, "xy": 6.0, "rgb": 0.1}
         self.base_lr, self.max_it, self.mu, self.wd = base_lr, max_iterations, momentum, weight_decay
@@ -125,9 +134,10 @@ class TrainEngine:
                 dist.all_reduce(flat)
 
     # ------------------------------------------------------------------ one optimiser step
-    def step(self, x, label_u8, beta=0.5, noise=None):
-        """One optimiser step: forward, loss, backward (+ gradient all-reduce), SGD (+EMA teacher), poly-LR update."""
-        self.forward_backward(x, label_u8, beta, noise)
+    def step(self, x, label_u8, beta=0.5, noise=None, weight=None):
+        """One optimiser step: forward, loss, backward (+ gradient all-reduce), SGD (+EMA teacher), poly-LR update.
+        weight ('s2l'): the loader's [N,H,W,C] batch of the running prediction average; read from `thr_iter` on."""
+        self.forward_backward(x, label_u8, beta, noise, weight)
         self.optimizer_step()
 
     def _noisy(self, x, noise, reps=1):
@@ -256,7 +266,7 @@ class TrainEngine:
                 rt.ptr(lws), nl, rt.stream())
         rt.call("wsl_axpy", rt.ptr(t["dz1"]), rt.ptr(t["dzx"]), 1.0, N * C_ * HW, rt.stream())
 
-    def forward_backward(self, x, label_u8, beta, noise=None):
+    def forward_backward(self, x, label_u8, beta=0.5, noise=None, weight=None):
         """Everything up to (and including) the gradient all-reduce; flat_grads() then holds the SUM over ranks."""
         m = self.model
         x = rt.f32c(x, "image batch")
@@ -264,6 +274,7 @@ class TrainEngine:
         HW = H * W
         t = self._tensors(N, H, W)
         m.train()
+        self._patch = (H, W)
         if self.loss_kind == "mean_teacher":
             self._start_teacher(x, noise)
         outs = m._run_forward(x, keep_for_backward=True)
@@ -276,6 +287,16 @@ class TrainEngine:
             self._ustm_losses(x, label_u8, z1, t, noise, lws, nl)
         elif self.loss_kind in self.REGULARISED:
             self._regularised_losses(x, label_u8, z1, t, lws, nl)
+        elif self.loss_kind == "s2l" and self.it >= self.thr_iter:      # train_s2l.py:125-147 (iter_num before its increment)
+            if weight is None:
+                raise _lib.WslError(f"'s2l' from thr_iter = {self.thr_iter} on needs step(..., weight=the loader's weight batch)")
+            weight = rt.f32c(weight, "weight batch")
+            if tuple(weight.shape) != (N, H, W, m.class_num):
+                raise _lib.WslError(f"weight batch {tuple(weight.shape)}, expected channels-last {(N, H, W, m.class_num)}")
+            ns = rt.L().wsl_s2l_head_ws_bytes(N, m.class_num, HW)
+            rt.call("wsl_s2l_head_fwd_bwd", rt.ptr(z1), rt.ptr(label_u8), rt.ptr(weight), self.ignore, float(self.thr_conf),
+                    self.s2l_w_u, 1.0, rt.ptr(self.loss_out), None, rt.ptr(t["dz1"]), N, m.class_num, HW,
+                    rt.ptr(rt.workspace("s2l_head", ns)), ns, rt.stream())
         elif self.loss_kind == "pce_gatedcrf":            # pCE + crf_weight * GatedCRF(y): one fused entry point
             d = self.crf_desc
             rt.call("wsl_head_gatedcrf_fwd_bwd", rt.ptr(z1), rt.ptr(z2), rt.ptr(label_u8), self.ignore, float(beta), rt.ptr(x),
@@ -286,7 +307,71 @@ class TrainEngine:
             rt.call("wsl_head_fwd_bwd", rt.ptr(z1), rt.ptr(z2), rt.ptr(label_u8), self.ignore, float(beta), w_pse, 1.0,
                     rt.ptr(self.loss_out), None, rt.ptr(t["dz1"]), rt.ptr(t["dz2"]), N, m.class_num, HW, rt.ptr(lws), nl,
                     rt.stream())
+        self._s2l_fused = self.loss_kind == "s2l" and self.it >= self.thr_iter
         self._finish_backward(x, t)
+
+    # ------------------------------------------------------------------ Scribble2Label: the running prediction average
+    def ensemble_due(self):
+        """train_s2l.py:214: after a step, `iter_num > 0 and iter_num % period_iter == 0` (iter_num already incremented)"""
+        return self.it > 0 and self.it % self.period_iter == 0
+
+    def update_ensemble(self, dataset, mode="reference", masks=None, patch_size=None, batch_size=32):
+        """Refresh the `weight` store of every slice of `dataset` (a BaseDataSets_s2l) from the current model
+        (ref: train_s2l.py:214-243): image zoomed with order 0 to the patch size, pred = softmax(model(image)), pred zoomed back
+        with order 0 to the slice's native size, weight = alpha * pred + (1 - alpha) * weight in fp32.
+
+        mode="reference": what the reference does, literally -- its model is in train() mode during this pass, so every slice is
+        ONE forward at N = 1 whose BatchNorm layers normalise by the slice's own statistics, whose running statistics take a
+        momentum update per slice, and whose dropout is live (drawn by the library; `masks`: a list with one entry per slice --
+        what the model's set_dropout_masks takes, a tuple for several arguments -- replays recorded masks in parity tests).
+        mode="eval": NOT what the reference does -- an opt-in departure: eval-mode forwards in batches of `batch_size`, no dropout,
+        BatchNorm from the running statistics, which stay untouched (as do all parameters and buffers).
+        patch_size: (H, W) of the network input; default: the last step's, else 256 x 256 (the reference hard-codes 256).
+        With several ranks every rank keeps and updates its own full store; there is no collective in this pass."""
+        if mode not in ("reference", "eval"):
+            raise ValueError(f"update_ensemble: mode {mode!r} (one of 'reference', 'eval')")
+        m, dev = self.model, rt.device()
+        Hn, Wn = patch_size or self._patch or (256, 256)
+        C_, n_all = m.class_num, len(dataset)
+        if masks is not None and (mode != "reference" or len(masks) != n_all):
+            raise _lib.WslError("update_ensemble: masks replay the reference-mode forwards, one entry per slice")
+        chunk = 64 if mode == "reference" else max(1, int(batch_size))      # slices per zoom launch / ensemble launch
+        was_training = m.training
+        m.train(mode == "reference")
+        try:
+            with torch.no_grad():
+                for b0 in range(0, n_all, chunk):
+                    idxs = list(range(b0, min(b0 + chunk, n_all)))
+                    n = len(idxs)
+                    aug = (_lib.WslAugSampleS2l * n)()
+                    slots = (_lib.WslS2lSlot * n)()
+                    hold = []
+                    for j, idx in enumerate(idxs):
+                        img = dataset.staged(idx)[0]
+                        w = dataset.images[idx]["weight"]
+                        if w.device != dev or w.dtype != torch.float32 or not w.is_contiguous() or \
+                                tuple(w.shape) != tuple(img.shape) + (C_,):
+                            raise _lib.WslError(f"slice {idx}: the weight store must be a contiguous float32 device tensor "
+                                                f"{tuple(img.shape) + (C_,)}, got {tuple(w.shape)} {w.dtype} on {w.device}")
+                        hold += [img, w]
+                        aug[j].img, aug[j].h, aug[j].w, aug[j].op = rt.ptr(img), img.shape[0], img.shape[1], 0
+                        slots[j].weight, slots[j].h, slots[j].w = rt.ptr(w), img.shape[0], img.shape[1]
+                    x = torch.empty((n, 1, Hn, Wn), dtype=torch.float32, device=dev)
+                    rt.call("wsl_augment_batch_s2l", aug, n, C_, rt.ptr(x), None, None, None, Hn, Wn, rt.stream())     # zoom(img, order=0)
+                    if mode == "eval":
+                        z = m._run_forward(x)[0]
+                    else:
+                        z = torch.empty((n, C_, Hn, Wn), dtype=torch.float32, device=dev)
+                        for j, idx in enumerate(idxs):
+                            if masks is not None:
+                                mk = masks[idx]
+                                m.set_dropout_masks(*mk) if isinstance(mk, tuple) else m.set_dropout_masks(mk)
+                            z[j:j + 1].copy_(m._run_forward(x[j:j + 1])[0])
+                    rt.call("wsl_s2l_ensemble_update", rt.ptr(z), slots, n, C_, Hn, Wn, float(self.s2l_alpha), rt.stream())
+        finally:
+            if masks is not None:
+                m.set_dropout_masks(None)
+            m.train(was_training)
 
     def _finish_backward(self, x, t):
         m = self.model
@@ -357,4 +442,7 @@ class TrainEngine:
         if self.loss_kind == "mean_teacher":   # tv / cons are the raw (unweighted) terms
             return {"loss": o[1] + self.tv_weight * o[4] + self._cons_w * o[5], "ce": o[1], "tv": o[4], "cons": o[5],
                     "n_valid": o[3]}
+        if self.loss_kind == "s2l":            # before thr_iter the second CE is not part of the loss: ce_u 0, n_u 0
+            f = self._s2l_fused
+            return {"loss": o[0], "ce": o[1], "ce_u": o[2] if f else 0.0, "n_valid": o[3], "n_u": o[4] if f else 0.0}
         return {"loss": o[0], "ce": o[1], "pse": o[2], "n_valid": o[3]}

@@ -299,3 +299,51 @@ class _Entropy(torch.autograd.Function):
 def entropy_loss(p, C=2):
     """mean(-sum_c p log(p+1e-6)) / log(C)  (ref: utils/losses.py:30-36), one fused kernel for value and gradient."""
     return _Entropy.apply(p, C)
+
+
+# --------------------------------------------------------------------------------------------------- Scribble2Label
+class _S2L(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, scribble, weight, thr_conf, w_u, ignore):
+        z = rt.f32c(z, "logits")
+        weight = rt.f32c(weight, "weight")
+        if scribble.dtype != torch.uint8:
+            scribble = scribble.to(torch.uint8)
+        scribble = scribble.contiguous()
+        N, C = z.shape[:2]
+        HW = z[0, 0].numel()
+        if weight.numel() != N * HW * C or weight.shape[-1] != C or scribble.numel() != N * HW:
+            raise _lib.WslError(f"s2l_loss: logits {tuple(z.shape)} need scribble [N,H,W] and a channels-last weight [N,H,W,{C}], "
+                                f"got {tuple(scribble.shape)} / {tuple(weight.shape)}")
+        n = rt.L().wsl_s2l_head_ws_bytes(N, C, HW)
+        ws = rt.workspace("s2l_head", n)
+        out = torch.empty(8, dtype=torch.float32, device=z.device)
+        u = torch.empty((N,) + tuple(z.shape[2:]), dtype=torch.uint8, device=z.device)
+        dz = torch.empty_like(z)
+        rt.call("wsl_s2l_head_fwd_bwd", rt.ptr(z), rt.ptr(scribble), rt.ptr(weight), int(ignore), float(thr_conf), float(w_u), 1.0,
+                rt.ptr(out), rt.ptr(u), rt.ptr(dz), N, C, HW, rt.ptr(ws), n, rt.stream())
+        ctx.save_for_backward(dz)
+        ctx.mark_non_differentiable(out, u)
+        return out[0], out, u
+
+    @staticmethod
+    def backward(ctx, g, _g_out, _g_u):
+        (dz,) = ctx.saved_tensors
+        return dz * g, None, None, None, None, None
+
+
+def s2l_head(logits, scribble, weight, thr_conf=0.8, w_u=0.5, ignore_index=4):
+    """The fused Scribble2Label loss head (one pass forward, one backward): returns (loss, parts[0:5] = {loss, ce, ce_u, n_valid,
+    n_u} on the device, u_labels uint8 [N,H,W])."""
+    return _S2L.apply(logits, scribble, weight, thr_conf, w_u, ignore_index)
+
+
+def s2l_loss(logits, scribble, weight, thr_conf=0.8, w_u=0.5, ignore_index=4):
+    """Scribble2Label loss from `thr_iter` on (ref: train_s2l.py:123-147):
+        loss = CE(logits, scribble, ignore) + w_u * CE(logits, u_labels, ignore),
+    u_labels[p] = the highest class c with weight[p, c] > float32(thr_conf) where scribble[p] == ignore, else ignore.  `weight` is the
+    loader's channels-last [N,H,W,C] float32 batch.  Each CE is a mean over its own valid pixels; with no confident pixel the second
+    one -- and the loss -- is NaN, as in the reference.  Returns (loss, loss_ce, loss_u); differentiable in `logits` (the gradient
+    flows through `loss`; loss_ce and loss_u are values)."""
+    loss, parts, _ = _S2L.apply(logits, scribble, weight, thr_conf, w_u, ignore_index)
+    return loss, parts[1], parts[2]
