@@ -85,6 +85,15 @@ def main(argv=None):
     val = BaseDataSets(base_dir=args.root_path, split="val", fold=args.fold, cache=True)
     if len(train) == 0:
         raise SystemExit("no training slices for this fold under " + args.root_path)
+    if not s2l and args.sup_type == "random_walker":     # ..._pCE_random_walker_2D.py: dense pseudo labels from the scribbles, solved once
+        import time as _time
+        from wsl4mis_amd.dataloaders.random_walker import precompute
+        t_rw = _time.time()
+        info = precompute(train, n_class=args.num_classes)
+        torch.cuda.synchronize()
+        if rank == 0:
+            print("random walker: %d slices labelled in %.2f s (%d zeroed by the class rule)"
+                  % (info["slices"], _time.time() - t_rw, info["zeroed_by_class_rule"]), flush=True)
     aug = BatchRandomGenerator_s2l(args.patch_size) if s2l else BatchRandomGenerator(args.patch_size, device_cache=True)
     eng = TrainEngine(args.model, 1, args.num_classes, base_lr=args.base_lr, max_iterations=args.max_iterations,
                       loss=args.loss, thr_iter=args.thr_iter, thr_conf=args.thr_conf, s2l_alpha=args.alpha, period_iter=args.period_iter)

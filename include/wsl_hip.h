@@ -422,6 +422,29 @@ typedef struct {
 int wsl_augment_batch_s2l(const WslAugSampleS2l* samples, int n, int C, float* out_img, uint8_t* out_mask, uint8_t* out_scr,
                           float* out_weight, int Ho, int Wo, void* stream);
 
+/* ------------------------------------------------------------------------------------------------ random-walker pseudo labels
+ * (ref: dataloaders/acdc_pseudo_label_random_walker.py:9-26 pseudo_label_generator_acdc, dataloaders/dataset_scribblevc.py:20-36 the
+ * prostate variant, :353-354,427-428 the call inside __getitem__; trainer: train_weakly_supervised_pCE_random_walker_2D.py:99-101.)
+ * skimage.segmentation.random_walker(data, markers, beta, mode='bf') on a single-channel 2-D image with unit spacing, for a batch of
+ * N equal-sized slices.  img [N, H, W] fp32, seed [N, H, W] uint8 with classes 0 .. n_class-1 and any value >= n_class = unlabelled.
+ *   class rule: a slice whose seeds lack one of the classes 1 .. n_class-1 gets label 0 (and probability 0) everywhere; nothing is solved
+ *   d = 2 * (clip(img, -0.35, 1.35) + 0.35) / 1.7 - 1                       (rescale_intensity to (-1, 1) with sigma = 0.35)
+ *   w_pq = exp(-beta * (d_p - d_q)^2 / (10 * std(d))) + 1e-6                on the 4-connected grid; std = population standard
+ *          deviation of the slice (accumulated in fp64).  std == 0 (a constant image): w = 1 + 1e-6 everywhere -- DELIBERATE, the
+ *          limit value; skimage divides by zero there and returns NaN.
+ *   L = D - W; for every class k:  L_uu x_k = -L_um [seed_m == k]          (u: unlabelled pixels, m: seeded ones)
+ *   label = argmax_k x_k (a tie goes to the lowest class) on unlabelled pixels, the seed itself on seeded ones.
+ * Solver: Jacobi-preconditioned conjugate gradients in fp32, one persistent workgroup per (slice, class) system; every dot product
+ * is reduced in a fixed order, so results are bit-reproducible.  A system stops when |r| <= tol * |b| (2-norms, r the recursively
+ * updated residual) or after max_iter iterations, whichever comes first: the loop always ends.  b == 0: x = 0 after 0 iterations.
+ * iters_out int32 [N, n_class] and resid_out fp32 [N, n_class] (the final |r| / |b|; 0 for b == 0 and for slices that fail the class
+ * rule) are always written -- the CALLER decides what a residual above tol means.  label_out uint8 [N, H, W]; prob_out fp32
+ * [N, n_class, H, W] or NULL (seeded pixels: one-hot).  2 <= H, W, H * W <= 2^20, 2 <= n_class <= 8, 0 <= max_iter <= 100000;
+ * anything else returns WSL_EUNSUPPORTED.  ws: wsl_random_walker_ws_bytes() (4 planes per slice + 4 per system). */
+size_t wsl_random_walker_ws_bytes(int N, int H, int W, int n_class);
+int wsl_random_walker(const float* img, const uint8_t* seed, uint8_t* label_out, float* prob_out, int* iters_out, float* resid_out,
+                      int N, int H, int W, int n_class, float beta, float tol, int max_iter, void* ws, size_t ws_bytes, void* stream);
+
 /* Validation metric pieces (medpy.metric.binary.hd95 as called by code/val_2D.py:7-15): the surface of a binary [D,H,W]
  * volume (object minus its erosion by the 6-neighbourhood, background outside the array) and, for every point of one
  * voxel list ([n][3] int64 z,y,x -- torch.nonzero layout), the exact squared distance to the nearest point of another.

@@ -162,6 +162,8 @@ _PROTOS = {
     "wsl_s2l_head_fwd_bwd": (i32, [c_fp, c_fp, c_fp, i32, f32, f32, f32, c_fp, c_fp, c_fp, i32, i32, i32, c_fp, sz, c_fp]),
     "wsl_s2l_ensemble_update": (i32, [c_fp, C.POINTER(WslS2lSlot), i32, i32, i32, i32, f64, c_fp]),
     "wsl_augment_batch_s2l": (i32, [C.POINTER(WslAugSampleS2l), i32, i32, c_fp, c_fp, c_fp, c_fp, i32, i32, c_fp]),
+    "wsl_random_walker_ws_bytes": (sz, [i32, i32, i32, i32]),
+    "wsl_random_walker": (i32, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, i32, i32, i32, i32, f32, f32, i32, c_fp, sz, c_fp]),
     "wsl_noisy_copy": (i32, [c_fp, c_fp, c_fp, i64, i32, f32, f32, C.c_uint64, c_fp]),
     "wsl_head_gatedcrf_fwd_bwd": (i32, [c_fp, c_fp, c_fp, i32, f64, c_fp, i32, f32, f32, f32, f32, c_fp, c_fp, c_fp, c_fp, c_fp,
                                         i32, i32, i32, i32, c_fp, sz, c_fp]),

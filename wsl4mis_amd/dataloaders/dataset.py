@@ -44,6 +44,9 @@ class BaseDataSets(Dataset):
         # cache=True (not in the reference): decoded arrays are kept in host memory after the first read -- h5lite inflates in
         # Python, and a 60000-iteration run touches each of the ~1500 slice files ~500 times
         self._cache = {} if cache else None
+        # sup_type="random_walker" on files without such a dataset: labels computed from image + scribble, once per case, kept in host
+        # memory whatever `cache` says (random_walker.precompute fills this in batches; otherwise the first read of a case does)
+        self._rw_cache = {}
         k = self.FOLDS.index(fold)
         test_ids = ["patient{:0>3}".format(i) for i in range(20 * k + 1, 20 * k + 21)]
         train_ids = [p for p in ("patient{:0>3}".format(i) for i in range(1, 101)) if p not in test_ids]
@@ -65,6 +68,11 @@ class BaseDataSets(Dataset):
     def __len__(self):
         return len(self.sample_list)
 
+    def _rw_inputs(self, case):
+        """(image, scribble) of a training slice whose file has no `random_walker` dataset, else None (random_walker.precompute)"""
+        with h5lite.File(os.path.join(self._base_dir, "ACDC_training_slices", case)) as f:
+            return None if "random_walker" in f else (f["image"][:], f["scribble"][:])
+
     def __getitem__(self, idx):
         case = self.sample_list[idx]
         if self._cache is not None and case in self._cache:
@@ -73,7 +81,14 @@ class BaseDataSets(Dataset):
             sub = "ACDC_training_slices" if self.split == "train" else "ACDC_training_volumes"
             with h5lite.File(os.path.join(self._base_dir, sub, case)) as f:
                 image = f["image"][:]
-                label = f[self.sup_type if self.split == "train" else "label"][:]
+                if self.split == "train" and self.sup_type == "random_walker" and "random_walker" not in f:
+                    # (ref: dataset_scribblevc.py:353-354 computes this on every read; the labels are deterministic, so once per case)
+                    label = self._rw_cache.get(case)
+                    if label is None:
+                        from .random_walker import pseudo_label_generator_acdc
+                        label = self._rw_cache[case] = pseudo_label_generator_acdc(image, f["scribble"][:])
+                else:
+                    label = f[self.sup_type if self.split == "train" else "label"][:]
             if self._cache is not None:
                 self._cache[case] = (image, label)
         sample = {"image": image, "label": label}
