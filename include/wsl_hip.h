@@ -452,6 +452,16 @@ int wsl_random_walker(const float* img, const uint8_t* seed, uint8_t* label_out,
 int wsl_surface_u8(const uint8_t* vol, uint8_t* border, int D, int H, int W, void* stream);
 int wsl_nearest_dist2(const int64_t* a_zyx, int na, const int64_t* b_zyx, int nb, int64_t* out, void* stream);
 
+/* The same with a voxel spacing, for the offline test stage (ref: code/test_2D_fully.py:74-80: medpy's asd and hd95 with
+ * voxelspacing = the NIfTI spacing in mm):  out[i] = min_j ((dz * sz)^2 + (dy * sy)^2) + (dx * sx)^2,  d* = a_i - b_j per axis.
+ * fp64 throughout; the integer difference is converted to double, multiplied by the spacing (one rounding), squared (one
+ * rounding) and the three terms are added in the order z, y, x, without FMA contraction: what
+ * scipy.ndimage.distance_transform_edt(sampling=...) evaluates for the feature it picks.  The result is bit-reproducible.
+ * Same [n][3] int64 z,y,x lists (array indices: 0 <= c < 2^31); a 2-D array passes z = 0 and any valid sz.  Both sets must be
+ * non-empty and every spacing finite and > 0, else WSL_EINVAL and nothing is written. */
+int wsl_nearest_dist2_sp(const int64_t* a_zyx, int na, const int64_t* b_zyx, int nb, double sz, double sy, double sx, double* out,
+                         void* stream);
+
 /* Noisy copies of a batch for the mean-teacher / USTM teachers (ref: train_mean_teacher_2D.py:147-149, ..._ustm_2D.py:125-135):
  * out[r*n + i] = x[i] + d,  r < reps, with d = noise[r*n + i] when `noise` is given (parity tests replay the reference's draw)
  * or clamp(N(0,1) * sigma, -clip, clip) drawn by the library (Philox4x32-10 + Box-Muller, reproducible per seed). */

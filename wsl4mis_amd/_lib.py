@@ -157,6 +157,7 @@ _PROTOS = {
     "wsl_sgd_step": (i32, [c_fp, c_fp, c_fp, i64, f32, f32, f32, i32, f32, c_fp, f32, c_fp]),
     "wsl_surface_u8": (i32, [c_fp, c_fp, i32, i32, i32, c_fp]),
     "wsl_nearest_dist2": (i32, [c_fp, i32, c_fp, i32, c_fp, c_fp]),
+    "wsl_nearest_dist2_sp": (i32, [c_fp, i32, c_fp, i32, f64, f64, f64, c_fp, c_fp]),
     "wsl_augment_batch": (i32, [C.POINTER(WslAugSample), i32, c_fp, c_fp, i32, i32, c_fp]),
     "wsl_s2l_head_ws_bytes": (sz, [i32, i32, i32]),
     "wsl_s2l_head_fwd_bwd": (i32, [c_fp, c_fp, c_fp, i32, f32, f32, f32, c_fp, c_fp, c_fp, i32, i32, i32, c_fp, sz, c_fp]),

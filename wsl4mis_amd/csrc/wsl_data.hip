@@ -94,6 +94,54 @@ __global__ __launch_bounds__(256) void nearest_d2_kernel(const int64_t* a, int n
   if (live) out[i] = best;
 }
 
+// The anisotropic sibling (ref: code/test_2D_fully.py:74-80: medpy's asd / hd95 with voxelspacing = the NIfTI spacing in mm):
+//   out[i] = min_j ((dz * sz)^2 + (dy * sy)^2) + (dx * sx)^2,   d* = a_i - b_j per axis
+// in fp64, every product and sum rounded on its own and added in the order z, y, x -- the expression
+// scipy.ndimage.distance_transform_edt(sampling=...) evaluates for the feature it picks (difference -> double, times the
+// spacing, squared, numpy.add.reduce over the axes).  The expression is compiled with floating-point contraction switched off
+// (sp_dist2: the __dmul_rn / __dadd_rn intrinsics are plain * and + to hipcc, which fuses them into v_fma_f64 under its default
+// -ffp-contract=fast-honor-pragmas); a minimum over identical expressions does not depend on the order, so the result is
+// bit-reproducible and equal to the host emulator's.
+// One a point per lane; b goes through LDS in tiles of kSpTile points, narrowed to int32 once while staging and stored per
+// axis, so that a wave reads four consecutive entries of one axis with one broadcast ds_read_b128 (all lanes the same address:
+// conflict-free).  A ragged tile is padded to a multiple of four with copies of its first point -- a duplicate cannot change a
+// minimum.  Coordinates are array indices (0 <= c < 2^31), as torch.nonzero returns them.
+constexpr int kSpTile = 1024;
+__device__ __forceinline__ double sp_dist2(int dz, int dy, int dx, double sz, double sy, double sx) {
+#pragma clang fp contract(off)
+  const double z = (double)dz * sz, y = (double)dy * sy, x = (double)dx * sx;
+  const double zz = z * z, yy = y * y, xx = x * x;
+  const double zy = zz + yy;
+  return zy + xx;
+}
+__global__ __launch_bounds__(256) void nearest_d2_sp_kernel(const int64_t* a, int na, const int64_t* b, int nb, double sz, double sy,
+                                                            double sx, double* out) {
+  __shared__ __attribute__((aligned(16))) int bz[kSpTile];
+  __shared__ __attribute__((aligned(16))) int by[kSpTile];
+  __shared__ __attribute__((aligned(16))) int bx[kSpTile];
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  const bool live = i < na;
+  const int az = live ? (int)a[3 * (int64_t)i] : 0, ay = live ? (int)a[3 * (int64_t)i + 1] : 0, ax = live ? (int)a[3 * (int64_t)i + 2] : 0;
+  double best = HUGE_VAL;
+  for (int j0 = 0; j0 < nb; j0 += kSpTile) {
+    const int m = nb - j0 < kSpTile ? nb - j0 : kSpTile, mp = (m + 3) & ~3;
+    __syncthreads();
+    for (int k = threadIdx.x; k < mp; k += kThreads) {
+      const int64_t* q = b + 3 * (int64_t)(j0 + (k < m ? k : 0));
+      bz[k] = (int)q[0], by[k] = (int)q[1], bx[k] = (int)q[2];
+    }
+    __syncthreads();
+    for (int j = 0; j < mp; j += 4) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const double d = sp_dist2(az - bz[j + u], ay - by[j + u], ax - bx[j + u], sz, sy, sx);
+        best = d < best ? d : best;
+      }
+    }
+  }
+  if (live) out[i] = best;
+}
+
 }  // namespace wsl
 
 using namespace wsl;
@@ -111,6 +159,15 @@ extern "C" int wsl_nearest_dist2(const int64_t* a_zyx, int na, const int64_t* b_
   WSL_REQUIRE(a_zyx && b_zyx && out && na > 0 && nb > 0, "nearest_dist2: both point sets must be non-empty");
   WSL_LAUNCH(nearest_d2_kernel, dim3(cdiv(na, kThreads)), dim3(kThreads), 0, stream, a_zyx, na, b_zyx, nb, out);
   return check_launch("nearest_d2_kernel");
+}
+
+extern "C" int wsl_nearest_dist2_sp(const int64_t* a_zyx, int na, const int64_t* b_zyx, int nb, double sz, double sy, double sx,
+                                    double* out, void* stream) {
+  WSL_REQUIRE(a_zyx && b_zyx && out && na > 0 && nb > 0, "nearest_dist2_sp: both point sets must be non-empty");
+  WSL_REQUIRE(isfinite(sz) && isfinite(sy) && isfinite(sx) && sz > 0.0 && sy > 0.0 && sx > 0.0,
+              "nearest_dist2_sp: the spacing must be finite and > 0 (got %g, %g, %g)", sz, sy, sx);
+  WSL_LAUNCH(nearest_d2_sp_kernel, dim3(cdiv(na, kThreads)), dim3(kThreads), 0, stream, a_zyx, na, b_zyx, nb, sz, sy, sx, out);
+  return check_launch("nearest_d2_sp_kernel");
 }
 
 extern "C" int wsl_augment_batch(const WslAugSample* samples, int n, float* out_img, uint8_t* out_lab, int Ho, int Wo,

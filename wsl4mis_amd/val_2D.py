@@ -4,7 +4,9 @@ per-class metrics over the volume.  The forward runs on the HIP path; the zoom (
 host-side glue.  medpy is not available offline: Dice is computed here, and HD95 follows medpy 0.4.0
 `metric.binary.hd95` (surface = object minus its 6-neighbourhood erosion; both directed sets of nearest-surface
 distances; 95th percentile with numpy's linear rule) with the two heavy pieces on the device (`wsl_surface_u8`,
-`wsl_nearest_dist2`: exact integer squared distances) and `torch.nonzero` / `torch.sort` as plumbing."""
+`wsl_nearest_dist2`: exact integer squared distances) and `torch.nonzero` / `torch.sort` as plumbing.  With a
+`voxelspacing` (the offline test stage, test_2D_fully.py: distances in millimetres) the nearest-surface search is
+`wsl_nearest_dist2_sp` in fp64; `asd_percase` is medpy's directed `asd`."""
 import numpy as np
 import torch
 from scipy.ndimage import zoom
@@ -22,8 +24,17 @@ def dice_percase(pred, gt):
     return 2.0 * inter / denom if denom else 0.0
 
 
+def _mask_u8(vol):
+    """a binary array (numpy, or a tensor already on the device) as a contiguous uint8 device tensor"""
+    if isinstance(vol, torch.Tensor):
+        if vol.device != rt.device():
+            raise rt._lib.WslError(f"mask lives on {vol.device}, expected {rt.device()}")
+        return (vol != 0).to(torch.uint8).contiguous()
+    return torch.as_tensor(np.ascontiguousarray(np.asarray(vol).astype(bool), dtype=np.uint8)).to(rt.device())
+
+
 def _surface_points(vol_bool):
-    v = torch.as_tensor(np.ascontiguousarray(vol_bool, dtype=np.uint8)).to(rt.device())
+    v = _mask_u8(vol_bool)
     if v.dim() not in (2, 3):
         raise NotImplementedError(f"hd95 of a {v.dim()}-D array is not built (2-D masks and [D,H,W] volumes are)")
     depth = 0 if v.dim() == 2 else v.shape[0]          # D = 0: a 2-D array -> 4-neighbourhood erosion, like medpy
@@ -34,22 +45,55 @@ def _surface_points(vol_bool):
     return torch.nonzero(border).contiguous()          # [n, 3] int64 (z, y, x)
 
 
-def hd95_percase(pred, gt, voxelspacing=None):
-    """medpy.metric.binary.hd95(result, reference) for isotropic unit voxels (what val_2D.py:12 passes)."""
-    if voxelspacing is not None:
-        raise NotImplementedError("voxelspacing is not built (the reference's validation never passes it)")
-    pred, gt = np.asarray(pred).astype(bool), np.asarray(gt).astype(bool)
-    if not pred.any():
+def _spacing(voxelspacing, ndim):
+    """scipy.ndimage's _normalize_sequence, which medpy applies first: a scalar counts for every axis, a sequence must have
+    one entry per axis (RuntimeError otherwise).  None stays None: the unit-spacing integer path."""
+    if voxelspacing is None:
+        return None
+    if isinstance(voxelspacing, str) or not hasattr(voxelspacing, "__iter__") or np.ndim(voxelspacing) == 0:
+        return (float(voxelspacing),) * ndim
+    sp = tuple(float(v) for v in voxelspacing)
+    if len(sp) != ndim:
+        raise RuntimeError("sequence argument must have length equal to input rank")
+    return sp
+
+
+def _surfaces(pred, gt, voxelspacing):
+    """medpy's __surface_distances up to the distance transform, in its order: spacing normalised, emptiness checked, both surfaces"""
+    nd = pred.dim() if isinstance(pred, torch.Tensor) else np.ndim(pred)
+    sp = _spacing(voxelspacing, nd)
+    pred, gt = _mask_u8(pred), _mask_u8(gt)
+    if not bool(pred.any()):
         raise RuntimeError("The first supplied array does not contain any binary object.")
-    if not gt.any():
+    if not bool(gt.any()):
         raise RuntimeError("The second supplied array does not contain any binary object.")
-    a, b = _surface_points(pred), _surface_points(gt)
-    d = []
-    for p, q in ((a, b), (b, a)):
+    return _surface_points(pred), _surface_points(gt), sp
+
+
+def _nearest(p, q, sp):
+    """fp64 distance from every point of p to the nearest point of q ([n, 3] surface lists); sp: None or one spacing per array axis"""
+    if sp is None:                                      # exact integer squared distances
         out = torch.empty((p.shape[0],), dtype=torch.int64, device=p.device)
         rt.call("wsl_nearest_dist2", rt.ptr(p), p.shape[0], rt.ptr(q), q.shape[0], rt.ptr(out), rt.stream())
-        d.append(out)
-    dist, _ = torch.sort(torch.sqrt(torch.cat(d).double()))
+        return torch.sqrt(out.double())
+    sz, sy, sx = sp if len(sp) == 3 else (1.0,) + tuple(sp)      # a 2-D array: z = 0 for every point
+    out = torch.empty((p.shape[0],), dtype=torch.float64, device=p.device)
+    rt.call("wsl_nearest_dist2_sp", rt.ptr(p), p.shape[0], rt.ptr(q), q.shape[0], sz, sy, sx, rt.ptr(out), rt.stream())
+    return torch.sqrt(out)
+
+
+def surface_distances(pred, gt, voxelspacing=None):
+    """medpy 0.4.0 `__surface_distances(result, reference, voxelspacing)`: for every surface voxel of `pred` (C order) the
+    distance to the nearest surface voxel of `gt`, as an fp64 tensor on the device.  voxelspacing: None (unit voxels, the exact
+    integer kernel), a scalar or one value per array axis (`wsl_nearest_dist2_sp`: the expression scipy's
+    distance_transform_edt(sampling=...) evaluates, so the values equal medpy's bit for bit unless scipy picked the other of two
+    near-tied features).  Masks are numpy arrays or tensors already on the device."""
+    a, b, sp = _surfaces(pred, gt, voxelspacing)
+    return _nearest(a, b, sp)
+
+
+def _percentile95(dist):
+    dist, _ = torch.sort(dist)
     n = dist.numel()
     pos = 0.95 * (n - 1)                                # numpy.percentile(..., 95), method 'linear'
     lo = int(np.floor(pos))
@@ -58,6 +102,25 @@ def hd95_percase(pred, gt, voxelspacing=None):
     lo_v, hi_v = float(dist[lo]), float(dist[hi])
     diff = hi_v - lo_v
     return hi_v - diff * (1 - t) if t >= 0.5 else lo_v + diff * t
+
+
+def hd95_percase(pred, gt, voxelspacing=None):
+    """medpy.metric.binary.hd95(result, reference, voxelspacing): None = isotropic unit voxels (what val_2D.py:12 passes)."""
+    a, b, sp = _surfaces(pred, gt, voxelspacing)
+    return _percentile95(torch.cat([_nearest(a, b, sp), _nearest(b, a, sp)]))
+
+
+def asd_percase(pred, gt, voxelspacing=None):
+    """medpy.metric.binary.asd(result, reference, voxelspacing): the mean of the DIRECTED pred -> gt surface distances (not assd)."""
+    return float(surface_distances(pred, gt, voxelspacing).mean())
+
+
+def hd95_asd_percase(pred, gt, voxelspacing=None):
+    """(hd95, asd) of one mask pair from one evaluation of the surfaces and of the pred -> gt distances (the reference's
+    calculate_metric_percase, test_2D_fully.py:74-80, computes them once per metric)."""
+    a, b, sp = _surfaces(pred, gt, voxelspacing)
+    d_ab = _nearest(a, b, sp)
+    return _percentile95(torch.cat([d_ab, _nearest(b, a, sp)])), float(d_ab.mean())
 
 
 def metric_percase(pred, gt, with_hd95=True):
