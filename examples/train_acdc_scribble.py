@@ -7,6 +7,8 @@ code/train_weakly_supervised_pCE_WSL4MIS (ours_proposed) / ..._pCE_GatedCRFLoss_
 --loss s2l is the flow of code/train_s2l.py (Scribble2Label): BaseDataSets_s2l keeps a running prediction average per training slice,
 BatchRandomGenerator_s2l carries it through the augmentation, the engine reads it from --thr_iter on and refreshes it after every
 --period_iter steps (TrainEngine.update_ensemble).
+--loss pce_interintra is the flow of code/train_weakly_supervised_pCE_Inter&Intra_Class_2D.py: pCE + w(t) * (inter-class variance -
+intra-class variance of image * softmax), w(t) = --consistency * sigmoid_rampup(iteration // 150, --consistency_rampup), on unet (or pnet).
 
     python examples/train_acdc_scribble.py --root_path <.../data/ACDC> --fold fold1 --max_iterations 60000
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/train_acdc_scribble.py ...
@@ -24,7 +26,7 @@ import torch
 import torch.distributed as dist
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from wsl4mis_amd import val_2D  # noqa: E402
+from wsl4mis_amd import _lib, val_2D  # noqa: E402
 from wsl4mis_amd.dataloaders.dataset import BaseDataSets, BatchRandomGenerator  # noqa: E402
 from wsl4mis_amd.dataloaders.dataset_s2l import BaseDataSets_s2l, BatchRandomGenerator_s2l  # noqa: E402
 from wsl4mis_amd.engine import TrainEngine  # noqa: E402
@@ -35,9 +37,13 @@ def main(argv=None):
     ap.add_argument("--root_path", required=True)
     ap.add_argument("--fold", default="fold1")
     ap.add_argument("--sup_type", default="scribble")
-    ap.add_argument("--model", default=None, choices=["unet_cct", "unet", "pnet"], help="default: unet_cct, and unet for --loss s2l "
-                    "(Scribble2Label trains a single-decoder net: unet or pnet)")
-    ap.add_argument("--loss", default="ours_proposed", choices=["ours_proposed", "pce", "pce_gatedcrf", "pce_tv", "pce_ms", "pce_entropy", "ce_dice", "mean_teacher", "ustm", "s2l"])
+    ap.add_argument("--model", default=None, choices=["unet_cct", "unet", "pnet"], help="default: unet_cct, and unet for --loss s2l / "
+                    "pce_interintra (single-decoder compositions: unet or pnet)")
+    ap.add_argument("--loss", default="ours_proposed", choices=["ours_proposed", "pce", "pce_gatedcrf", "pce_tv", "pce_ms", "pce_entropy", "ce_dice", "mean_teacher", "ustm", "s2l", "pce_interintra"])
+    # inter/intra-class variance (train_weakly_supervised_pCE_Inter&Intra_Class_2D.py:62-65)
+    ap.add_argument("--consistency", type=float, default=0.1, help="pce_interintra: the weight's plateau")
+    ap.add_argument("--consistency_rampup", type=float, default=200.0, help="pce_interintra: length of the sigmoid ramp in units of 150 "
+                    "iterations (0 = constant weight)")
     # Scribble2Label (train_s2l.py:62-65)
     ap.add_argument("--period_iter", type=int, default=100)
     ap.add_argument("--thr_iter", type=int, default=6000)
@@ -68,10 +74,11 @@ def main(argv=None):
     ap.add_argument("--resume", default=None, help="a state_dict .pth (the reference's or ours: same keys) to start from")
     args = ap.parse_args(argv)
     if args.model is None:
-        args.model = "unet" if args.loss == "s2l" else "unet_cct"
+        args.model = "unet" if args.loss in ("s2l", "pce_interintra") else "unet_cct"
 
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
-    torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
+    if not _lib.is_test_emulation():          # (the test-suite can run this loop against the host-emulation library on CPU tensors)
+        torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group("nccl")
@@ -96,7 +103,8 @@ def main(argv=None):
                   % (info["slices"], _time.time() - t_rw, info["zeroed_by_class_rule"]), flush=True)
     aug = BatchRandomGenerator_s2l(args.patch_size) if s2l else BatchRandomGenerator(args.patch_size, device_cache=True)
     eng = TrainEngine(args.model, 1, args.num_classes, base_lr=args.base_lr, max_iterations=args.max_iterations,
-                      loss=args.loss, thr_iter=args.thr_iter, thr_conf=args.thr_conf, s2l_alpha=args.alpha, period_iter=args.period_iter)
+                      loss=args.loss, thr_iter=args.thr_iter, thr_conf=args.thr_conf, s2l_alpha=args.alpha, period_iter=args.period_iter,
+                      var_consistency=args.consistency, var_rampup=args.consistency_rampup)
     if args.resume:
         eng.model.load_state_dict(torch.load(args.resume, map_location="cpu"))
     if args.snapshot_path and rank == 0:

@@ -314,10 +314,15 @@ int wsl_gatedcrf_bwd(const float* msg, const float* gout, float gscale, float* d
  * train_mean_teacher_2D.py:147-171).  The head's first pass keeps softmax(z) in `s`, the regulariser kernels turn it into the weighted
  * gradient `ds`, the head's second pass writes dz = w_ce * dCE/dz + softmax_backward(s, ds) once: instead of the chain
  * head -> softmax -> R -> softmax-backward -> axpy (-> softmax-MSE -> axpy) three to five launches and as many passes over [N,C,H,W] fewer.
- * out[0..3] as wsl_head_fwd_bwd (single branch), out[4] = R (unweighted), out[5] = the consistency term (unweighted; only with zt). */
+ * out[0..3] as wsl_head_fwd_bwd (single branch), out[4] = R (unweighted), out[5] = the consistency term (unweighted; only with zt).
+ * WSL_REG_CLASS_VAR: R = inter_class_variance(softmax, image) - intra_class_variance(softmax, image) (wsl_class_variance_fwd_bwd below;
+ * ref: train_weakly_supervised_pCE_Inter&Intra_Class_2D.py:30-37,112-118): reg_weight = w means (w_inter, w_intra) = (w, -w), img is
+ * required, C >= 2 and H * W >= 2, and `out` holds EIGHT floats: out[4] = inter - intra, out[6] = inter, out[7] = intra (all unweighted;
+ * out[5] as for the other kinds). */
 #define WSL_REG_TV 1
 #define WSL_REG_MS 2
 #define WSL_REG_ENTROPY 3
+#define WSL_REG_CLASS_VAR 4
 int wsl_head_reg_fwd_bwd(const float* z, const uint8_t* label, int ignore, float w_ce, int reg_kind, float reg_weight,
                          const float* img, const float* zt, float cons_weight, float* out, float* dz, float* s, float* ds, int N,
                          int C, int H, int W, void* ws, size_t ws_bytes, void* stream);
@@ -327,6 +332,27 @@ int wsl_tv_fwd_bwd(const float* p, int n0, float* loss, float* dp, float gscale,
 /* MumfordShah_Loss().forward(image, prediction) (ref: utils/losses.py:275-309). */
 int wsl_mumford_shah_fwd_bwd(const float* img, const float* p, float* loss, float* dp, float gscale, int N, int C, int H,
                              int W, void* ws, size_t ws_bytes, void* stream);
+/* inter_class_variance / intra_class_variance of the inter/intra-class trainer (ref: train_weakly_supervised_pCE_Inter&Intra_Class_2D.py:
+ * 30-37).  p [N,C,H,W] is already a softmax, img [N,1,H,W]; M = H * W, q = img * p (image broadcast over the classes):
+ *   mu[n,c] = sum_i q / M              sigma[n,c] = sqrt(sum_i (q - mu)^2 / (M - 1))         intra = mean_{n,c} sigma
+ *   mbar[n] = mean_c mu[n,c]           tau[n]     = sqrt(sum_c (mu - mbar)^2 / (C - 1))      inter = mean_n tau
+ * (torch.std: unbiased).  loss[0..2] = {inter - intra, inter, intra}.  dp = w_inter * d inter/dp + w_intra * d intra/dp, written, not
+ * accumulated (dp == NULL: values only; dp may not alias p):
+ *   d inter / d p[n,c,i] = img[n,i] * (mu[n,c] - mbar[n]) / ((C-1) * tau[n] * N * M)
+ *   d intra / d p[n,c,i] = img[n,i] * (q[n,c,i] - mu[n,c]) / ((M-1) * sigma[n,c] * N * C)
+ * The reference's term with weight w is (w_inter, w_intra) = (w, -w).
+ * ZERO VARIANCE IS PART OF THE CONTRACT: where sigma[n,c] == 0 (an all-zero image slice) or tau[n] == 0 (equal class means, e.g. all-zero
+ * logits) that term's value is 0 and its gradient is exactly 0 -- what torch.std returns; no NaN leaves the kernels for finite inputs.
+ * C < 2 or H * W < 2 (torch returns NaN there) and C > 8: WSL_EINVAL, nothing written.  Multi-channel images and a gradient with respect
+ * to the image are not built (the Python layer raises NotImplementedError).
+ * Three launches: per (sample, 4096-pixel chunk) CENTRED moments (chunk mean, chunk M2 per class, fp32, q held in registers between the
+ * two block reductions -- the one-pass sum q^2 - (sum q)^2 / M form loses 1e-4 on near-constant q), one workgroup that merges the chunk
+ * pairs in chunk order with the pairwise update of Chan et al. in fp64 and writes the values and per-(n,c) coefficients, one elementwise
+ * gradient pass.  Fixed order, no float atomics: bit-reproducible.  ws: wsl_loss_ws_bytes (the moments start where the Mumford-Shah
+ * moments live). */
+int wsl_class_variance_fwd_bwd(const float* img, const float* p, float* loss /* 3 floats: inter - intra, inter, intra */,
+                               float* dp, float w_inter, float w_intra, int N, int C, int H, int W,
+                               void* ws, size_t ws_bytes, void* stream);
 /* mean((softmax(a)-softmax(b))^2) and its gradient wrt a (ref: utils/losses.py:65-82, train_mean_teacher_2D.py:164). */
 int wsl_softmax_mse_fwd_bwd(const float* a, const float* b, float* loss, float* da, float gscale, int N, int C, int HW,
                             void* ws, size_t ws_bytes, void* stream);

@@ -821,6 +821,167 @@ __global__ __launch_bounds__(256) void ms_main_kernel(const float* img, const fl
   }
 }
 
+// ------------------------------------------------------------------------------------------------ inter / intra class variance
+// inter_class_variance(p, img) - intra_class_variance(p, img) of the inter/intra-class trainer (ref:
+// train_weakly_supervised_pCE_Inter&Intra_Class_2D.py:30-37,112-118), q = img * p:
+//   intra = mean_{n,c} std_i(q[n,c,i]),   inter = mean_n std_c(mean_i q[n,c,i])      (torch.std: unbiased)
+// Three kernels in the shape of the Mumford-Shah pair above: grid (chunks, N), 256 threads, 4096-pixel chunks.
+//   cv_moment_kernel   per (n, chunk) and class the CENTRED pair (chunk mean, chunk M2 = sum (q - chunk mean)^2) in fp32 from ONE read of
+//                      p and img: a thread keeps its 16 pixels x C values of q in registers between the two block reductions.  (The
+//                      one-pass sum q^2 - (sum q)^2 / M form in fp32 is off by 3e-5 .. 2e-4 on a near-constant q; this one by < 1e-7.)
+//   cv_coef_kernel     one workgroup: the chunk pairs merged in chunk order with the pairwise update of Chan et al. in fp64, the three
+//                      loss values, and per (n, c) the coefficients {mu, a, b} of the closed-form gradient
+//                        a = w_inter (mu - mbar) / ((C-1) tau N M),   b = w_intra / ((M-1) sigma N C),   0 where tau / sigma == 0
+//   cv_grad_kernel     dp = img * (a + b * (q - mu)), elementwise
+// Fixed order, no float atomics: bit-reproducible.
+constexpr int kCvChunk = 4096, kCvPer = kCvChunk / kThreads;
+
+// sums of K per-thread values over the workgroup with two barriers for all of them: wave sums, then the four waves in a fixed order
+template <int K>
+__device__ __forceinline__ void block_sum_k(float (&v)[K], float* red) {   // red: 4 * K floats
+  const int w = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < K; ++k) v[k] = wave_sum(v[k]);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) red[w * K + k] = v[k];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < K; ++k) v[k] = (red[k] + red[K + k]) + (red[2 * K + k] + red[3 * K + k]);
+}
+
+template <int C>
+__global__ __launch_bounds__(256) void cv_moment_kernel(const float* img, const float* p, int HW, int chunks, float* mom) {  // mom[n][chunk][C][2]
+  __shared__ float red[4 * C];
+  const int n = blockIdx.y, base = blockIdx.x * kCvChunk;
+  const int cnt = HW - base < kCvChunk ? HW - base : kCvChunk;
+  float q[kCvPer][C], s[C];
+#pragma unroll
+  for (int c = 0; c < C; ++c) s[c] = 0.f;
+#pragma unroll
+  for (int k = 0; k < kCvPer; ++k) {
+    const int i = base + k * kThreads + (int)threadIdx.x;
+    const bool in = i < HW;
+    const float I = in ? img[(int64_t)n * HW + i] : 0.f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      q[k][c] = in ? I * p[((int64_t)n * C + c) * HW + i] : 0.f;
+      s[c] += q[k][c];
+    }
+  }
+  block_sum_k<C>(s, red);
+  float mean[C], m2[C];
+#pragma unroll
+  for (int c = 0; c < C; ++c) mean[c] = s[c] / (float)cnt, m2[c] = 0.f;
+#pragma unroll
+  for (int k = 0; k < kCvPer; ++k) {
+    const bool in = base + k * kThreads + (int)threadIdx.x < HW;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      const float d = q[k][c] - mean[c];
+      m2[c] = in ? fmaf(d, d, m2[c]) : m2[c];
+    }
+  }
+  block_sum_k<C>(m2, red);
+  if (threadIdx.x == 0) {
+    float* o = mom + ((int64_t)n * chunks + blockIdx.x) * C * 2;
+#pragma unroll
+    for (int c = 0; c < C; ++c) o[2 * c] = mean[c], o[2 * c + 1] = m2[c];
+  }
+}
+
+struct CvP {
+  int N, C, HW, chunks;
+  float w_inter, w_intra;
+};
+
+// stat[N*C][2]: mu as an fp32 pair (hi + lo carries the fp64 value to ~48 bits; the workspace is only float-aligned); coef[N*C][3] = {mu, a, b}
+__global__ __launch_bounds__(256) void cv_coef_kernel(const float* mom, CvP q, float* stat, float* coef, float* l_diff, float* l_inter,
+                                                      float* l_intra) {
+  __shared__ double red[kThreads];
+  const int NC = q.N * q.C;
+  const double M = (double)q.HW, Nd = (double)q.N, Cd = (double)q.C;
+  double intra = 0, inter = 0;
+  for (int j = threadIdx.x; j < NC; j += kThreads) {
+    const int n = j / q.C, c = j - n * q.C;
+    double cnt = 0, mean = 0, m2 = 0;
+    for (int k = 0; k < q.chunks; ++k) {     // Chan et al.: merge (cnt, mean, m2) with chunk k's (nb, mb, m2b)
+      const float* m = mom + (((int64_t)n * q.chunks + k) * q.C + c) * 2;
+      const int left = q.HW - k * kCvChunk;
+      const double nb = (double)(left < kCvChunk ? left : kCvChunk), mb = (double)m[0], m2b = (double)m[1];
+      const double tot = cnt + nb, delta = mb - mean;
+      mean += delta * (nb / tot);
+      m2 += m2b + delta * delta * (cnt * nb / tot);
+      cnt = tot;
+    }
+    const double sigma = sqrt(m2 / (M - 1.0));
+    intra += sigma;
+    const float hi = (float)mean;
+    stat[2 * j] = hi, stat[2 * j + 1] = (float)(mean - (double)hi);
+    coef[3 * j] = hi;
+    coef[3 * j + 2] = sigma > 0 ? (float)((double)q.w_intra / ((M - 1.0) * sigma * Nd * Cd)) : 0.f;
+  }
+  __syncthreads();   // the means of every class of a sample, written by other threads of this (only) workgroup
+  for (int j = threadIdx.x; j < NC; j += kThreads) {
+    const int n = j / q.C, c = j - n * q.C;
+    // Welford over the classes: equal means give mbar == mu and tau == 0 EXACTLY (the zero-variance rule of the contract)
+    double mbar = 0, s2 = 0, mine = 0;
+    for (int cc = 0; cc < q.C; ++cc) {
+      const float* st = stat + 2 * ((int64_t)n * q.C + cc);
+      const double mu = (double)st[0] + (double)st[1], d = mu - mbar;
+      mbar += d / (double)(cc + 1);
+      s2 += d * (mu - mbar);
+      if (cc == c) mine = mu;
+    }
+    const double tau = sqrt(s2 / (Cd - 1.0));
+    coef[3 * j + 1] = tau > 0 ? (float)((double)q.w_inter * (mine - mbar) / ((Cd - 1.0) * tau * Nd * M)) : 0.f;
+    if (c == 0) inter += tau;
+  }
+  const double ia = block_sum_d2(intra, red) / (Nd * Cd), ie = block_sum_d2(inter, red) / Nd;
+  if (threadIdx.x == 0) l_diff[0] = (float)(ie - ia), l_inter[0] = (float)ie, l_intra[0] = (float)ia;
+}
+
+// VEC: HW % 4 == 0 and 16-byte aligned tensors -- one float4 of every class plane per thread; else four strided scalars per thread
+template <bool VEC>
+__global__ __launch_bounds__(256) void cv_grad_kernel(const float* img, const float* p, const float* coef, int C, int HW, float* dp) {
+  const int n = blockIdx.y;
+  if (VEC) {
+    const int i = ((int)blockIdx.x * kThreads + (int)threadIdx.x) * 4;
+    if (i >= HW) return;
+    const float4 I = *reinterpret_cast<const float4*>(img + (int64_t)n * HW + i);
+    for (int c = 0; c < C; ++c) {
+      const float* k = coef + ((int64_t)n * C + c) * 3;
+      float mu = k[0], a = k[1], b = k[2];
+      // (three scalars loaded side by side: cut them loose from their register pairs before they are broadcast over the float4 -- hipcc
+      //  otherwise forms v_pk_fma_f32 with op_sel on src2, the unsafe form of wsl_rt.h's hardware rule)
+      WSL_DETACH32(mu);
+      WSL_DETACH32(a);
+      WSL_DETACH32(b);
+      const int64_t o = ((int64_t)n * C + c) * HW + i;
+      const float4 pv = *reinterpret_cast<const float4*>(p + o);
+      float4 g;
+      g.x = I.x * fmaf(b, fmaf(I.x, pv.x, -mu), a);
+      g.y = I.y * fmaf(b, fmaf(I.y, pv.y, -mu), a);
+      g.z = I.z * fmaf(b, fmaf(I.z, pv.z, -mu), a);
+      g.w = I.w * fmaf(b, fmaf(I.w, pv.w, -mu), a);
+      *reinterpret_cast<float4*>(dp + o) = g;
+    }
+  } else {
+    for (int u = 0; u < 4; ++u) {
+      const int i = (int)blockIdx.x * kThreads * 4 + u * kThreads + (int)threadIdx.x;
+      if (i >= HW) return;
+      const float I = img[(int64_t)n * HW + i];
+      for (int c = 0; c < C; ++c) {
+        const float* k = coef + ((int64_t)n * C + c) * 3;
+        const int64_t o = ((int64_t)n * C + c) * HW + i;
+        dp[o] = I * fmaf(k[2], fmaf(I, p[o], -k[0]), k[1]);
+      }
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ softmax MSE
 __global__ __launch_bounds__(256) void softmax_mse_kernel(const float* a, const float* b, int C, int HW, int64_t P,
                                                           float k, float* da, float* part) {
@@ -1032,6 +1193,11 @@ using namespace wsl;
 // Floats in front of the free part of the workspace: the head's partials and its 64 coefficients (`scal`), which every fused entry point
 // keeps alive between its passes.
 constexpr size_t kHeadFloats = (size_t)kMaxBlocks * kMaxK + 64;
+
+// inter / intra class variance (defined next to wsl_class_variance_fwd_bwd below; the fused regulariser head uses them too)
+static size_t cv_floats(int N, int C, int chunks);
+static void cv_launch(const float* img, const float* p, float* l_diff, float* l_inter, float* l_intra, float* dp, float w_inter,
+                      float w_intra, int N, int C, int H, int W, float* region, void* stream);
 
 // Workgroups per sample the GatedCRF kernels can launch on an image of HW pixels, whatever its aspect ratio: the generic kernel's
 // cdiv(W, 32) * cdiv(H, 8) tiles (the 4-class kernel's 32 x 32 tiles are never more).  W <= 32: one tile column, cdiv(H, 8) <= cdiv(HW, 8);
@@ -1271,8 +1437,11 @@ extern "C" int wsl_head_reg_fwd_bwd(const float* z, const uint8_t* label, int ig
                                     const float* img, const float* zt, float cons_weight, float* out, float* dz, float* s, float* ds,
                                     int N, int C, int H, int W, void* ws, size_t ws_bytes, void* stream) {
   WSL_REQUIRE(z && label && out && dz && s && ds && N > 0 && H > 0 && W > 0 && C > 0 && C <= kMaxC, "head_reg_fwd_bwd: bad args");
-  WSL_REQUIRE(reg_kind >= WSL_REG_TV && reg_kind <= WSL_REG_ENTROPY, "head_reg_fwd_bwd: reg_kind %d", reg_kind);
+  WSL_REQUIRE(reg_kind >= WSL_REG_TV && reg_kind <= WSL_REG_CLASS_VAR, "head_reg_fwd_bwd: reg_kind %d", reg_kind);
   WSL_REQUIRE(reg_kind != WSL_REG_MS || img, "head_reg_fwd_bwd: Mumford-Shah needs the image");
+  const bool cvar = reg_kind == WSL_REG_CLASS_VAR;
+  WSL_REQUIRE(!cvar || (img && C >= 2 && (int64_t)H * W >= 2 && (int64_t)H * W <= (1 << 30) && N <= 65535),
+              "head_reg_fwd_bwd: the class-variance term needs the image, at least 2 classes and 2 pixels");
   const int HW = H * W, HW_ = HW;
   WSL_WS_OK("head_reg_fwd_bwd");
   HeadP h{z, nullptr, label, ignore, C, HW, N, (int64_t)N * HW, 0.f, 1.f};
@@ -1288,11 +1457,18 @@ extern "C" int wsl_head_reg_fwd_bwd(const float* z, const uint8_t* label, int ig
   // its GatedCRF partials at the same offset as `mom`.)
   const int chunks = cdiv(HW, 4096);
   float* mom = scal + 64;
-  const size_t rneed = (size_t)N * C * cdiv(W, 16) * cdiv(H, 16) + (size_t)N * chunks * 2 + kMaxBlocks;
+  // (the class-variance kernels keep their moments and coefficients in [mom ..): the only partials left are the consistency term's, which
+  //  fit the head's dead region)
+  const size_t rneed = cvar ? (size_t)kMaxBlocks : (size_t)N * C * cdiv(W, 16) * cdiv(H, 16) + (size_t)N * chunks * 2 + kMaxBlocks;
   float* rpart = rneed <= (size_t)kMaxBlocks * kMaxK ? part : mom + (size_t)N * chunks * (kMaxC + 1);
   if ((size_t)(rpart - part) + rneed > ws_bytes / sizeof(float)) {
     set_error("head_reg_fwd_bwd: workspace %zu < %zu (the regulariser's partials of %d x %d x %d x %d)", ws_bytes,
               sizeof(float) * ((size_t)(rpart - part) + rneed), N, C, H, W);
+    return WSL_EWORKSPACE;
+  }
+  if (cvar && kHeadFloats + cv_floats(N, C, chunks) > ws_bytes / sizeof(float)) {
+    set_error("head_reg_fwd_bwd: workspace %zu < %zu (class-variance moments of %d x %d x %d x %d)", ws_bytes,
+              sizeof(float) * (kHeadFloats + cv_floats(N, C, chunks)), N, C, H, W);
     return WSL_EWORKSPACE;
   }
   {   // pass 1: softmax (kept in s), partial-CE sums -> the head's coefficients
@@ -1312,6 +1488,8 @@ extern "C" int wsl_head_reg_fwd_bwd(const float* z, const uint8_t* label, int ig
       WSL_LAUNCH(ms_moment_kernel, dim3(chunks, N), dim3(kThreads), 0, stream, img, s, C, HW, chunks, mom);
       WSL_LAUNCH(ms_main_kernel, dim3(chunks, N), dim3(kThreads), 0, stream, img, s, mom, C, H, W, chunks, reg_weight, ds, rpart);
       WSL_LAUNCH(sum_finalize_kernel, dim3(1), dim3(kThreads), 0, stream, rpart, N * chunks, 2, 1.0, out + 4);
+    } else if (cvar) {   // out[4] = inter - intra, out[6] = inter, out[7] = intra; ds = reg_weight * d(inter - intra)/ds
+      cv_launch(img, s, out + 4, out + 6, out + 7, ds, reg_weight, -reg_weight, N, C, H, W, mom, stream);
     } else {
       const double norm = 1.0 / ((double)h.P * log((double)C));
       WSL_LAUNCH(entropy_kernel, dim3(nb), dim3(kThreads), 0, stream, s, C, HW, h.P, (float)(reg_weight * norm), ds, rpart);
@@ -1362,6 +1540,58 @@ extern "C" int wsl_mumford_shah_fwd_bwd(const float* img, const float* p, float*
   WSL_LAUNCH(ms_main_kernel, dim3(chunks, N), dim3(kThreads), 0, stream, img, p, mom, C, H, W, chunks, gscale, dp, part);
   WSL_LAUNCH(sum_finalize_kernel, dim3(1), dim3(kThreads), 0, stream, part, N * chunks, 2, 1.0, loss);
   return check_launch("mumford_shah_fwd_bwd");
+}
+
+// ---- inter / intra class variance (kernels: cv_*).  Workspace (floats) behind the head's partials and coefficients, i.e. starting where
+// the Mumford-Shah moments live: [chunk moments: N * chunks * C * 2][means as fp32 pairs: N * C * 2][coefficients: N * C * 3].  At C > 4 the
+// moments are longer than the kMaxC + 1 floats per (sample, chunk) of the Mumford-Shah region and run on into the spare room behind it;
+// wsl_loss_ws_bytes holds them for every shape (N * C * (2 chunks + 5) <= N * (16 chunks + 40) against N * (41 chunks + 98) floats there, as
+// cdiv(HW, 256) >= 16 chunks - 15) -- and the bound is checked against the launch's real chunk count before anything is launched.
+static size_t cv_floats(int N, int C, int chunks) { return (size_t)N * C * (2 * (size_t)chunks + 5); }
+
+static void cv_launch(const float* img, const float* p, float* l_diff, float* l_inter, float* l_intra, float* dp, float w_inter,
+                      float w_intra, int N, int C, int H, int W, float* region, void* stream) {
+  const int HW = H * W, chunks = cdiv(HW, kCvChunk);
+  float* mom = region;
+  float* stat = mom + (size_t)N * chunks * C * 2;
+  float* coef = stat + (size_t)N * C * 2;
+  const dim3 grid(chunks, N), blk(kThreads);
+  switch (C) {
+    case 2: WSL_LAUNCH((cv_moment_kernel<2>), grid, blk, 0, stream, img, p, HW, chunks, mom); break;
+    case 3: WSL_LAUNCH((cv_moment_kernel<3>), grid, blk, 0, stream, img, p, HW, chunks, mom); break;
+    case 4: WSL_LAUNCH((cv_moment_kernel<4>), grid, blk, 0, stream, img, p, HW, chunks, mom); break;
+    case 5: WSL_LAUNCH((cv_moment_kernel<5>), grid, blk, 0, stream, img, p, HW, chunks, mom); break;
+    case 6: WSL_LAUNCH((cv_moment_kernel<6>), grid, blk, 0, stream, img, p, HW, chunks, mom); break;
+    case 7: WSL_LAUNCH((cv_moment_kernel<7>), grid, blk, 0, stream, img, p, HW, chunks, mom); break;
+    default: WSL_LAUNCH((cv_moment_kernel<8>), grid, blk, 0, stream, img, p, HW, chunks, mom); break;
+  }
+  CvP q{N, C, HW, chunks, w_inter, w_intra};
+  WSL_LAUNCH(cv_coef_kernel, dim3(1), blk, 0, stream, mom, q, stat, coef, l_diff, l_inter, l_intra);
+  if (!dp) return;
+  const bool vec = (HW & 3) == 0 && ((reinterpret_cast<uintptr_t>(img) | reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(dp)) & 15) == 0;
+  const dim3 ggrid(cdiv(HW, 4 * kThreads), N);
+  if (vec) WSL_LAUNCH((cv_grad_kernel<true>), ggrid, blk, 0, stream, img, p, coef, C, HW, dp);
+  else WSL_LAUNCH((cv_grad_kernel<false>), ggrid, blk, 0, stream, img, p, coef, C, HW, dp);
+}
+
+extern "C" int wsl_class_variance_fwd_bwd(const float* img, const float* p, float* loss, float* dp, float w_inter, float w_intra, int N,
+                                          int C, int H, int W, void* ws, size_t ws_bytes, void* stream) {
+  WSL_REQUIRE(img && p && loss && N > 0 && N <= 65535 && H > 0 && W > 0 && (int64_t)H * W <= (1 << 30) && dp != p,
+              "class_variance: bad args");
+  WSL_REQUIRE(C >= 2 && C <= kMaxC && (int64_t)H * W >= 2,
+              "class_variance: C = %d, H * W = %lld (an unbiased standard deviation needs 2 <= C <= %d classes and 2 pixels)", C,
+              (long long)H * W, kMaxC);
+  const int HW_ = H * W;
+  WSL_WS_OK("class_variance_fwd_bwd");
+  const size_t need = kHeadFloats + cv_floats(N, C, cdiv(HW_, kCvChunk));
+  if (need > ws_bytes / sizeof(float)) {
+    set_error("class_variance_fwd_bwd: workspace %zu < %zu (moments of %d x %d x %d x %d)", ws_bytes, sizeof(float) * need, N, C, H, W);
+    return WSL_EWORKSPACE;
+  }
+  // values: one read of p + img; gradient: a second read and the write of dp
+  ProfScope ps(PF_LOSS_HEAD, 0.0, (double)N * HW_ * (4.0 * C + 4.0) * (dp ? 2.0 : 1.0) + (dp ? 4.0 * C * N * HW_ : 0.0), stream);
+  cv_launch(img, p, loss, loss + 1, loss + 2, dp, w_inter, w_intra, N, C, H, W, static_cast<float*>(ws) + kHeadFloats, stream);
+  return check_launch("class_variance_fwd_bwd");
 }
 
 extern "C" int wsl_softmax_mse_fwd_bwd(const float* a, const float* b, float* loss, float* da, float gscale, int N, int C,

@@ -17,6 +17,12 @@ Steps reproduced (reference file:line, all under code/):
   's2l'             train_s2l.py:123-147,214-243 (Scribble2Label; unet | pnet): pCE while it < thr_iter, then pCE + 0.5 * CE on the
                     pseudo labels thresholded from the running prediction average `weight` (step(..., weight=w));
                     update_ensemble(dataset) is that average's refresh, due after every step with it % period_iter == 0
+  'pce_interintra'  train_weakly_supervised_pCE_Inter&Intra_Class_2D.py:30-37,112-118 (unet | pnet): pCE + w(t) * (inter_class_variance
+                    (softmax, image) - intra_class_variance(softmax, image)), w(t) = var_consistency * sigmoid_rampup(it // 150,
+                    var_rampup) with `it` before its increment (var_rampup = 0: the constant weight).  One fused call
+                    (wsl_head_reg_fwd_bwd, WSL_REG_CLASS_VAR); fused_heads = False runs the chain head -> softmax ->
+                    wsl_class_variance_fwd_bwd -> softmax backward -> axpy.  Zero-variance terms (an all-zero image slice, equal
+                    class means) contribute 0 and no gradient, as torch.std does
 Optimiser: SGD(lr, momentum 0.9, wd 1e-4) with the poly schedule applied one step late (ours_proposed.py:126-132).
 
 Data parallel (DDP-equivalent semantics): one process per GPU, per-rank BatchNorm statistics and loss
@@ -48,8 +54,8 @@ class TrainEngine:
     def __init__(self, net_type="unet_cct", in_chns=1, class_num=4, base_lr=0.01, max_iterations=60000, momentum=0.9,
                  weight_decay=1e-4, loss="ours_proposed", w_pse=0.5, crf_radius=5, crf_weight=0.1,
                  crf_desc=None, ignore_index=4, model=None, force_dp=False, conv_precision="f32", thr_iter=6000, thr_conf=0.8,
-                 s2l_alpha=0.2, period_iter=100):
-        if loss not in ("ours_proposed", "pce", "pce_gatedcrf", "mean_teacher", "ustm", "s2l") + self.REGULARISED:
+                 s2l_alpha=0.2, period_iter=100, var_consistency=0.1, var_rampup=200.0):
+        if loss not in ("ours_proposed", "pce", "pce_gatedcrf", "mean_teacher", "ustm", "s2l", "pce_interintra") + self.REGULARISED:
             raise NotImplementedError(f"loss composition '{loss}'")
         # conv_precision: "f32" (default, the headline path) | "split_f16x3" (opt-in: networks/unet.py, include/wsl_hip.h)
         self.model = model if model is not None else net_factory(net_type, in_chns, class_num, conv_precision=conv_precision)
@@ -63,7 +69,11 @@ class TrainEngine:
             raise _lib.WslError(f"'{loss}' is a single-branch (unet) composition")
         if loss == "s2l" and self.dual:
             raise _lib.WslError("'s2l' is a single-decoder composition (unet, pnet)")
+        if loss == "pce_interintra" and self.dual:
+            raise _lib.WslError("'pce_interintra' is a single-decoder composition (unet, pnet)")
         self.loss_kind, self.w_pse, self.ignore = loss, w_pse, ignore_index
+        # inter/intra-class variance (..._pCE_Inter&Intra_Class_2D.py:62-70 --consistency / --consistency_rampup, :115 the ramp's argument)
+        self.var_consistency, self.var_rampup, self._var_w, self._var_slot = var_consistency, var_rampup, 0.0, 4
         # Scribble2Label (train_s2l.py:62-65): threshold iteration / confidence, EMA weight of the store, update period; w_u: :147
         self.thr_iter, self.thr_conf, self.s2l_alpha, self.period_iter, self.s2l_w_u = thr_iter, thr_conf, s2l_alpha, period_iter, 0.5
         self._s2l_fused, self._patch = False, None
@@ -111,7 +121,7 @@ class TrainEngine:
                 t["s"], t["ds"], t["dzx"] = mk(), mk(), mk()
             if self.loss_kind == "ustm":
                 t["zr"], t["dzx"], t["pm"] = mk(), mk(), mk()
-            if self.loss_kind in self.REGULARISED:
+            if self.loss_kind in self.REGULARISED or self.loss_kind == "pce_interintra":
                 t["s"], t["ds"], t["dzx"] = mk(), mk(), mk()
             self._bufs = {key: t}
         return self._bufs[key]
@@ -212,6 +222,33 @@ class TrainEngine:
         rt.call("wsl_softmax_bwd", rt.ptr(t["s"]), rt.ptr(t["ds"]), rt.ptr(t["dzx"]), N, C_, HW, rt.stream())
         rt.call("wsl_axpy", rt.ptr(t["dz1"]), rt.ptr(t["dzx"]), 1.0, N * C_ * HW, rt.stream())
 
+    def var_weight(self, it=None):
+        """w(t) of 'pce_interintra': get_current_consistency_weight(iter_num // 150) of the trainer (lines 68-70, 115)"""
+        from .utils.ramps import sigmoid_rampup
+        return self.var_consistency * sigmoid_rampup((self.it if it is None else it) // 150, self.var_rampup)
+
+    def _interintra_losses(self, x, label_u8, z, t, lws, nl):
+        """pCE + w(t) * (inter_class_variance(softmax, image) - intra_class_variance(softmax, image))"""
+        N, H, W = x.shape[0], x.shape[2], x.shape[3]
+        HW, C_ = H * W, self.model.class_num
+        if x.shape[1] != 1:
+            raise NotImplementedError("the class-variance terms are built for a single-channel image")
+        lo, w = self.loss_out, self.var_weight()
+        self._var_w = w
+        if self.fused_heads:      # out[4] = inter - intra, out[6] = inter, out[7] = intra
+            self._var_slot = 4
+            rt.call("wsl_head_reg_fwd_bwd", rt.ptr(z), rt.ptr(label_u8), self.ignore, 1.0, 4, w, rt.ptr(x), None, 0.0, rt.ptr(lo),
+                    rt.ptr(t["dz1"]), rt.ptr(t["s"]), rt.ptr(t["ds"]), N, C_, H, W, rt.ptr(lws), nl, rt.stream())
+            return
+        self._var_slot = 5        # the stand-alone entry point writes {inter - intra, inter, intra} contiguously: slots 5, 6, 7
+        rt.call("wsl_head_fwd_bwd", rt.ptr(z), None, rt.ptr(label_u8), self.ignore, 0.0, 0.0, 1.0, rt.ptr(lo), None,
+                rt.ptr(t["dz1"]), None, N, C_, HW, rt.ptr(lws), nl, rt.stream())
+        rt.call("wsl_softmax_fwd", rt.ptr(z), rt.ptr(t["s"]), N, C_, HW, rt.stream())
+        rt.call("wsl_class_variance_fwd_bwd", rt.ptr(x), rt.ptr(t["s"]), rt.ptr(lo[5:]), rt.ptr(t["ds"]), w, -w, N, C_, H, W,
+                rt.ptr(lws), nl, rt.stream())
+        rt.call("wsl_softmax_bwd", rt.ptr(t["s"]), rt.ptr(t["ds"]), rt.ptr(t["dzx"]), N, C_, HW, rt.stream())
+        rt.call("wsl_axpy", rt.ptr(t["dz1"]), rt.ptr(t["dzx"]), 1.0, N * C_ * HW, rt.stream())
+
     def _ustm_losses(self, x, label_u8, z, t, noise, lws, nl):
         """train_weakly_supervised_ustm_2D.py:119-157: pCE + w(t) * uncertainty-masked consistency.  `noise`: None (drawn
         like the script) or a list of T//2 + 1 tensors (teacher input noise, then the T//2 double-batch noises)."""
@@ -287,6 +324,8 @@ class TrainEngine:
             self._ustm_losses(x, label_u8, z1, t, noise, lws, nl)
         elif self.loss_kind in self.REGULARISED:
             self._regularised_losses(x, label_u8, z1, t, lws, nl)
+        elif self.loss_kind == "pce_interintra":
+            self._interintra_losses(x, label_u8, z1, t, lws, nl)
         elif self.loss_kind == "s2l" and self.it >= self.thr_iter:      # train_s2l.py:125-147 (iter_num before its increment)
             if weight is None:
                 raise _lib.WslError(f"'s2l' from thr_iter = {self.thr_iter} on needs step(..., weight=the loader's weight batch)")
@@ -437,6 +476,9 @@ class TrainEngine:
             return {"loss": 0.5 * (o[1] + o[4]), "ce": o[1], "dice": o[4], "n_valid": o[3]}
         if self.loss_kind in self.REGULARISED:  # reg is the raw (unweighted) regulariser
             return {"loss": o[1] + self.REG_WEIGHT[self.loss_kind] * o[4], "ce": o[1], "reg": o[4], "n_valid": o[3]}
+        if self.loss_kind == "pce_interintra":  # reg = inter - intra (unweighted), w = the weight the step used
+            return {"loss": o[1] + self._var_w * o[self._var_slot], "ce": o[1], "reg": o[self._var_slot], "inter": o[6], "intra": o[7],
+                    "w": self._var_w, "n_valid": o[3]}
         if self.loss_kind == "ustm":           # cons is the raw (unweighted) masked consistency; n_certain = sum(mask)
             return {"loss": o[1] + self._cons_w * o[4], "ce": o[1], "cons": o[4], "n_certain": o[5], "n_valid": o[3]}
         if self.loss_kind == "mean_teacher":   # tv / cons are the raw (unweighted) terms

@@ -7,6 +7,7 @@ do not implement raise NotImplementedError instead of being ignored.
     MumfordShah_Loss()(image, prediction)                                ref: utils/losses.py:275-309
     softmax_mse_loss(input_logits, target_logits, sigmoid=False)         ref: utils/losses.py:65-82
     entropy_loss(p, C=2)                                                 ref: utils/losses.py:30-36
+    inter_class_variance(prob, img), intra_class_variance(prob, img)     ref: ...pCE_Inter&Intra_Class_2D.py:30-37 (defined in the trainer)
 plus the pieces the trainers take from torch / define inline:
     PartialCrossEntropyLoss(ignore_index)(logits, target)                ref: ...pCE_2D.py:81,100 (CrossEntropyLoss)
     tv_loss(prediction)                                                  ref: ...pCE_TV_2D.py:58-65
@@ -299,6 +300,61 @@ class _Entropy(torch.autograd.Function):
 def entropy_loss(p, C=2):
     """mean(-sum_c p log(p+1e-6)) / log(C)  (ref: utils/losses.py:30-36), one fused kernel for value and gradient."""
     return _Entropy.apply(p, C)
+
+
+# --------------------------------------------------------------------------------------------------- inter / intra class variance
+class _ClassVariance(torch.autograd.Function):
+    """(inter, intra) of wsl_class_variance_fwd_bwd as two outputs: the forward is the value-only call, the backward ONE gradient call with
+    (w_inter, w_intra) = the two incoming gradients -- any linear combination of the two back-propagates with one pass over prob."""
+
+    @staticmethod
+    def forward(ctx, prob, img):
+        prob, img = rt.f32c(prob, "prob"), rt.f32c(img, "img")
+        N, C, H, W = prob.shape
+        ws, n = _lws(N, C, H * W)
+        out = torch.empty(3, dtype=torch.float32, device=prob.device)
+        rt.call("wsl_class_variance_fwd_bwd", rt.ptr(img), rt.ptr(prob), rt.ptr(out), None, 0.0, 0.0, N, C, H, W, rt.ptr(ws), n,
+                rt.stream())
+        ctx.save_for_backward(prob, img)
+        return out[1], out[2]
+
+    @staticmethod
+    def backward(ctx, g_inter, g_intra):
+        prob, img = ctx.saved_tensors
+        N, C, H, W = prob.shape
+        ws, n = _lws(N, C, H * W)
+        out, dp = torch.empty(3, dtype=torch.float32, device=prob.device), torch.empty_like(prob)
+        rt.call("wsl_class_variance_fwd_bwd", rt.ptr(img), rt.ptr(prob), rt.ptr(out), rt.ptr(dp), float(g_inter), float(g_intra), N, C,
+                H, W, rt.ptr(ws), n, rt.stream())
+        return dp, None
+
+
+def _class_variance(prob, img):
+    if prob.dim() != 4 or tuple(img.shape) != (prob.shape[0], 1, prob.shape[2], prob.shape[3]):
+        raise NotImplementedError(f"the class-variance terms are built for prob [N,C,H,W] and a single-channel image [N,1,H,W], got "
+                                  f"{tuple(prob.shape)} / {tuple(img.shape)}")
+    if img.requires_grad:
+        raise NotImplementedError("gradient with respect to the image is not built")
+    return _ClassVariance.apply(prob, img)
+
+
+def inter_class_variance(prob, img):
+    """mean over n of the unbiased std over classes of the per-class pixel means of img * prob (ref: the trainer's function of this name).
+    Zero variance (equal class means) gives 0 with a zero gradient; C < 2 is refused (torch returns NaN)."""
+    return _class_variance(prob, img)[0]
+
+
+def intra_class_variance(prob, img):
+    """mean over (n, c) of the unbiased std over pixels of img * prob (ref: the trainer's function of this name).  A constant plane (an
+    all-zero image slice) contributes 0 with a zero gradient; H * W < 2 is refused (torch returns NaN)."""
+    return _class_variance(prob, img)[1]
+
+
+def class_variance_loss(prob, img):
+    """inter_class_variance(prob, img) - intra_class_variance(prob, img): the trainer's consistency term, one kernel call forward and one
+    backward."""
+    inter, intra = _class_variance(prob, img)
+    return inter - intra
 
 
 # --------------------------------------------------------------------------------------------------- Scribble2Label
