@@ -9,6 +9,12 @@ BatchRandomGenerator_s2l carries it through the augmentation, the engine reads i
 --period_iter steps (TrainEngine.update_ensemble).
 --loss pce_interintra is the flow of code/train_weakly_supervised_pCE_Inter&Intra_Class_2D.py: pCE + w(t) * (inter-class variance -
 intra-class variance of image * softmax), w(t) = --consistency * sigmoid_rampup(iteration // 150, --consistency_rampup), on unet (or pnet).
+--loss semi_mt | semi_uamt | semi_entmin is the flow of code/train_mean_teacher_2D.py, train_uncertainty_aware_mean_teacher_2D.py and
+train_entropy_minimization_2D.py (code/train_semi.sh): two datasets (labeled_type "labeled" with dense labels, "unlabeled"), two loaders of
+--batch_size // 2 each, zip(cycle(labeled), unlabeled); the student runs on both halves, 0.5 * (CE + Dice) on the labeled one and
+w(t) * the consistency / entropy term on the unlabeled one, w(t) = --consistency * sigmoid_rampup(iteration // 300, --consistency_rampup).
+--teacher_update frozen is the reference's scripts to the letter (they never call update_ema_variables); the default ema is the method.
+(train_partially_fully_supervised.py is --loss ce_dice --sup_type label --labeled_type labeled.)
 
     python examples/train_acdc_scribble.py --root_path <.../data/ACDC> --fold fold1 --max_iterations 60000
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/train_acdc_scribble.py ...
@@ -39,11 +45,16 @@ def main(argv=None):
     ap.add_argument("--sup_type", default="scribble")
     ap.add_argument("--model", default=None, choices=["unet_cct", "unet", "pnet"], help="default: unet_cct, and unet for --loss s2l / "
                     "pce_interintra (single-decoder compositions: unet or pnet)")
-    ap.add_argument("--loss", default="ours_proposed", choices=["ours_proposed", "pce", "pce_gatedcrf", "pce_tv", "pce_ms", "pce_entropy", "ce_dice", "mean_teacher", "ustm", "s2l", "pce_interintra"])
+    ap.add_argument("--loss", default="ours_proposed", choices=["ours_proposed", "pce", "pce_gatedcrf", "pce_tv", "pce_ms", "pce_entropy", "ce_dice", "mean_teacher", "ustm", "s2l", "pce_interintra",
+                                                                     "semi_mt", "semi_uamt", "semi_entmin"])
     # inter/intra-class variance (train_weakly_supervised_pCE_Inter&Intra_Class_2D.py:62-65)
-    ap.add_argument("--consistency", type=float, default=0.1, help="pce_interintra: the weight's plateau")
-    ap.add_argument("--consistency_rampup", type=float, default=200.0, help="pce_interintra: length of the sigmoid ramp in units of 150 "
-                    "iterations (0 = constant weight)")
+    ap.add_argument("--consistency", type=float, default=0.1, help="pce_interintra / semi_*: the weight's plateau")
+    ap.add_argument("--consistency_rampup", type=float, default=200.0, help="pce_interintra / semi_*: length of the sigmoid ramp in units of "
+                    "150 (semi_*: 300) iterations (0 = constant weight)")
+    # semi-supervised trainers (train_mean_teacher_2D.py:60-66)
+    ap.add_argument("--ema_decay", type=float, default=0.99)
+    ap.add_argument("--teacher_update", default="ema", choices=["ema", "frozen"], help="semi_mt / semi_uamt: 'frozen' = the reference's "
+                    "scripts literally (update_ema_variables is defined and never called: the teacher keeps its initial weights)")
     # Scribble2Label (train_s2l.py:62-65)
     ap.add_argument("--period_iter", type=int, default=100)
     ap.add_argument("--thr_iter", type=int, default=6000)
@@ -74,7 +85,7 @@ def main(argv=None):
     ap.add_argument("--resume", default=None, help="a state_dict .pth (the reference's or ours: same keys) to start from")
     args = ap.parse_args(argv)
     if args.model is None:
-        args.model = "unet" if args.loss in ("s2l", "pce_interintra") else "unet_cct"
+        args.model = "unet" if args.loss in ("s2l", "pce_interintra") or args.loss.startswith("semi_") else "unet_cct"
 
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     if not _lib.is_test_emulation():          # (the test-suite can run this loop against the host-emulation library on CPU tensors)
@@ -83,8 +94,14 @@ def main(argv=None):
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group("nccl")
     random.seed(args.seed), np.random.seed(args.seed + rank), torch.manual_seed(args.seed)
-    s2l = args.loss == "s2l"
-    if s2l:      # every slice of the fold's training patients, held in memory with its weight store (train_s2l.py:86-87)
+    s2l, semi = args.loss == "s2l", args.loss.startswith("semi_")
+    unlabeled = None
+    if semi:     # train_mean_teacher_2D.py:106-115: the labeled patients with their dense masks, the unlabeled ones for their images
+        train = BaseDataSets(base_dir=args.root_path, split="train", fold=args.fold, sup_type="label", labeled_type="labeled", cache=True)
+        unlabeled = BaseDataSets(base_dir=args.root_path, split="train", fold=args.fold, sup_type="label", labeled_type="unlabeled", cache=True)
+        if len(unlabeled) == 0:
+            raise SystemExit("no unlabeled training slices for this fold under " + args.root_path)
+    elif s2l:      # every slice of the fold's training patients, held in memory with its weight store (train_s2l.py:86-87)
         train = BaseDataSets_s2l(base_dir=args.root_path, fold=args.fold, class_num=args.num_classes)
     else:
         train = BaseDataSets(base_dir=args.root_path, split="train", fold=args.fold, sup_type=args.sup_type,
@@ -104,7 +121,8 @@ def main(argv=None):
     aug = BatchRandomGenerator_s2l(args.patch_size) if s2l else BatchRandomGenerator(args.patch_size, device_cache=True)
     eng = TrainEngine(args.model, 1, args.num_classes, base_lr=args.base_lr, max_iterations=args.max_iterations,
                       loss=args.loss, thr_iter=args.thr_iter, thr_conf=args.thr_conf, s2l_alpha=args.alpha, period_iter=args.period_iter,
-                      var_consistency=args.consistency, var_rampup=args.consistency_rampup)
+                      var_consistency=args.consistency, var_rampup=args.consistency_rampup, consistency=args.consistency,
+                      consistency_rampup=args.consistency_rampup, ema_decay=args.ema_decay, teacher_update=args.teacher_update)
     if args.resume:
         eng.model.load_state_dict(torch.load(args.resume, map_location="cpu"))
     if args.snapshot_path and rank == 0:
@@ -116,25 +134,55 @@ def main(argv=None):
     import time
     t_start = time.time()
     last = args.stop_iterations if 0 < args.stop_iterations < args.max_iterations else args.max_iterations
+    half = args.batch_size // 2
+    if semi and (half < 2 or len(train) < 2):
+        raise SystemExit("--loss semi_*: needs --batch_size >= 4 (two loaders of batch_size // 2 >= 2 slices: BatchNorm) and at least two "
+                         "labeled slices; got batch_size %d, %d labeled slices" % (args.batch_size, len(train)))
+
+    def labeled_batches():      # cycle(trainloader_labeled), reshuffled on every pass (a pass always yields: checked above)
+        while True:
+            pl = order.permutation(len(train))
+            for b in range(0, len(pl), half):
+                if len(pl[b:b + half]) >= 2:
+                    yield pl[b:b + half]
+
+    def batches():
+        """index batches of one epoch: (labeled or whole-batch indices, unlabeled indices or None)"""
+        if semi:                # zip(cycle(labeled), unlabeled): an epoch is one pass over the unlabeled slices
+            perm = order.permutation(len(unlabeled))
+            for b in range(0, len(perm), half):
+                yield next(lab_iter), perm[b:b + half]
+        else:
+            perm = order.permutation(len(train))
+            for b in range(0, len(perm), args.batch_size):
+                yield perm[b:b + args.batch_size], None
+
+    def train_step(idx, idx_u):
+        if semi:
+            image_u, _ = aug([unlabeled[int(i)] for i in idx_u])
+            image, label = aug([train[int(i)] for i in idx])
+            eng.step(image, label, unlabeled=image_u)
+            return
+        weight = None
+        if s2l:
+            image, _, label, weight = aug([train[int(i)] for i in idx])
+        else:
+            image, label = aug([train[int(i)] for i in idx])
+        if args.oracle_stream:
+            from wsl4mis_amd.networks.unet import _DROP, _FT
+            n, (ph, pw) = len(idx), args.patch_size
+            em = [(torch.rand((n, _FT[l], ph >> l, pw >> l)) >= _DROP[l]).to(torch.uint8).cuda() for l in range(5)]
+            eng.model.set_dropout_masks(em, None)
+        eng.step(image, label, random.random() + 1e-10, weight=weight)
+        if args.oracle_stream:
+            eng.model.set_dropout_masks(None, None)
+
+    lab_iter = labeled_batches() if semi else None
     while it < last:
-        perm = order.permutation(len(train))
-        for b in range(0, len(perm), args.batch_size):
-            idx = perm[b:b + args.batch_size]
-            if len(idx) < 2:                            # BatchNorm needs more than one slice
+        for idx, idx_u in batches():
+            if len(idx) < 2 or (idx_u is not None and len(idx_u) < 2):      # BatchNorm needs more than one slice
                 continue
-            weight = None
-            if s2l:
-                image, _, label, weight = aug([train[int(i)] for i in idx])
-            else:
-                image, label = aug([train[int(i)] for i in idx])
-            if args.oracle_stream:
-                from wsl4mis_amd.networks.unet import _DROP, _FT
-                n, (ph, pw) = len(idx), args.patch_size
-                em = [(torch.rand((n, _FT[l], ph >> l, pw >> l)) >= _DROP[l]).to(torch.uint8).cuda() for l in range(5)]
-                eng.model.set_dropout_masks(em, None)
-            eng.step(image, label, random.random() + 1e-10, weight=weight)
-            if args.oracle_stream:
-                eng.model.set_dropout_masks(None, None)
+            train_step(idx, idx_u)
             it += 1
             if s2l and eng.ensemble_due():              # train_s2l.py:214-243; every rank refreshes its own full store
                 eng.update_ensemble(train, mode=args.ensemble_mode, patch_size=tuple(args.patch_size))

@@ -374,6 +374,41 @@ int wsl_entropy_fwd_bwd(const float* p, float* loss, float* dp, float gscale, in
                         void* ws, size_t ws_bytes, void* stream);
 int wsl_axpy(float* dst, const float* src, float k, int64_t n, void* stream);
 
+/* ------------------------------------------------------------------------------------------------ semi-supervised heads
+ * The two loss heads the semi-supervised trainers add (ref: train_mean_teacher_2D.py:151-171,
+ * train_uncertainty_aware_mean_teacher_2D.py:151-190, train_entropy_minimization_2D.py:130-143), both straight from logits
+ * z [N,C,HW].  Same conventions as the loss entries above: no allocation, no synchronisation, per-workgroup partials merged by one
+ * workgroup in a fixed order in fp64, no float atomics -- bit-reproducible.  1 <= C <= 8: a larger C returns WSL_EINVAL and nothing
+ * is written.  ws: wsl_loss_ws_bytes(N, C, HW) -- both heads fit the shared loss workspace, there is no query of their own; a smaller
+ * one returns WSL_EWORKSPACE and nothing is written.  With HW % 4 == 0 and 16-byte aligned z / dz (4-byte aligned labels) the
+ * logits are read and the gradient written 128 bits per lane; any other shape or alignment takes the one-pixel-per-lane form.
+ *
+ * wsl_sup_head_fwd_bwd -- the labeled half (ref: train_mean_teacher_2D.py:161-163 with utils/losses.py:156-192 DiceLoss), on dense
+ * uint8 labels:
+ *   s = softmax(z);  ce = CrossEntropyLoss(ignore_index = ignore)(z, label): the mean NLL over the pixels with label != ignore;
+ *   dice = DiceLoss(C)(s, label) = mean_c (1 - (2 I_c + 1e-5) / (Z_c + Y_c + 1e-5)),  I_c = sum s_c [label == c],  Z_c = sum s_c^2,
+ *          Y_c = sum [label == c] over ALL pixels of the batch: the one-hot runs over range(C), so a pixel labelled `ignore` (or any
+ *          value >= C) is zero in every class and still counts in Z_c;
+ *   out[0..3] = {loss = w_ce * ce + w_dice * dice, ce, dice, n_valid};   dz = gscale * dloss/dz, written once (NULL: values only).
+ * A batch WITHOUT a valid pixel follows wsl_head_fwd_bwd: ce (and with it loss) is NaN like torch's, n_valid 0, and the CE part of
+ * the gradient is exactly 0 -- dz is then the Dice term's gradient alone and stays finite.
+ * Equals the chain wsl_head_fwd_bwd(w = w_ce) -> wsl_softmax_fwd -> wsl_pdice_fwd(ignore -1) -> wsl_pdice_bwd(gout = w_dice) ->
+ * wsl_softmax_bwd -> wsl_axpy to fp32 round-off in three launches: one pass reduces the NLL sum, the valid count and the 3 * C Dice
+ * sums, the merge does the scalar arithmetic, one pass recomputes the softmax and writes dz (no s / ds tensors at all).
+ *
+ * wsl_entropy_logits_fwd_bwd -- entropy_loss(softmax(z), norm_classes) (ref: utils/losses.py:30-36 as called by
+ * train_entropy_minimization_2D.py:140-142):
+ *   p = softmax(z);  loss[0] = sum_{n,i} ( -sum_c p_c log(p_c + 1e-6) ) / (N * HW * log(norm_classes));
+ *   dz = gscale * dloss/dz = k * p_c * (e_c - sum_j e_j p_j),  e_c = -(log(p_c + 1e-6) + p_c / (p_c + 1e-6)),
+ *   k = gscale / (N * HW * log(norm_classes))   (dz NULL: value only).
+ * The 1e-6 stays inside the logarithm and in the derivative, as the reference expression has it.  The normaliser is known before the
+ * launch, so ONE pass writes the gradient and the partial sums; the merge follows.  norm_classes < 2: WSL_EINVAL.
+ * Equals wsl_softmax_fwd -> wsl_entropy_fwd_bwd -> wsl_softmax_bwd. */
+int wsl_sup_head_fwd_bwd(const float* z, const uint8_t* label, int ignore, float w_ce, float w_dice, float gscale, float* out,
+                         float* dz, int N, int C, int HW, void* ws, size_t ws_bytes, void* stream);
+int wsl_entropy_logits_fwd_bwd(const float* z, float* loss, float* dz, float gscale, int N, int C, int HW, int norm_classes,
+                               void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------ optimiser
  * torch.optim.SGD(momentum, weight_decay) over a flat arena (ref: ...pCE_ours_proposed.py:89-90,126-132):
  *   g = grad*grad_scale + wd*p; buf = first ? g : mu*buf + g; p -= lr*buf;

@@ -23,6 +23,22 @@ Steps reproduced (reference file:line, all under code/):
                     (wsl_head_reg_fwd_bwd, WSL_REG_CLASS_VAR); fused_heads = False runs the chain head -> softmax ->
                     wsl_class_variance_fwd_bwd -> softmax backward -> axpy.  Zero-variance terms (an all-zero image slice, equal
                     class means) contribute 0 and no gradient, as torch.std does
+  'semi_mt' | 'semi_uamt' | 'semi_entmin'   the semi-supervised trainers (unet | pnet): step(x_l, label_l, unlabeled=x_u) runs the
+                    student TWICE, as the scripts do -- the labeled half with its own BatchNorm batch statistics, then the unlabeled
+                    half with its own -- loss = 0.5 * (CE(z_l, label) + DiceLoss(softmax(z_l), label)) + w(t) * U(z_u), with
+                    U = mean((softmax(z_u) - softmax(teacher(x_u + noise)))^2)                  train_mean_teacher_2D.py:147-171
+                      | the same distance masked by the teacher's uncertainty (T = 8 stochastic passes, no rot90)
+                                                                        train_uncertainty_aware_mean_teacher_2D.py:147-190
+                      | entropy_loss(softmax(z_u), 4)                                  train_entropy_minimization_2D.py:130-143
+                    and w(t) = consistency * sigmoid_rampup(it // 300, consistency_rampup), `it` before its increment.  The loss is
+                    a sum of a term of the first forward and a term of the second, so the step is forward(x_l) -> supervised head ->
+                    backward -> keep the gradient arena; forward(x_u) -> unsupervised head -> backward -> add the kept arena: the
+                    parameter gradient of the reference's single backward(), BatchNorm running statistics updated in the same order.
+                    wsl_sup_head_fwd_bwd / wsl_entropy_logits_fwd_bwd are the fused heads (fused_heads = False: the chains of calls).
+                    teacher_update: the reference's two mean-teacher scripts DEFINE update_ema_variables and never call it -- their
+                    teacher keeps its initial weights for the whole run.  "frozen" reproduces that literally (a step leaves the
+                    teacher's parameter arena bit-unchanged); "ema" (default) places the call as train_weakly_supervised_ustm_2D.py:163
+                    does, alpha = min(1 - 1 / (it + 1), ema_decay), which is what the method is
 Optimiser: SGD(lr, momentum 0.9, wd 1e-4) with the poly schedule applied one step late (ours_proposed.py:126-132).
 
 Data parallel (DDP-equivalent semantics): one process per GPU, per-rank BatchNorm statistics and loss
@@ -44,6 +60,7 @@ from .networks.net_factory import net_factory
 class TrainEngine:
     # pCE + weight * regulariser(softmax(outputs)) of the single-branch scripts: (weight, reference lines)
     REGULARISED = ("pce_tv", "pce_ms", "pce_entropy", "ce_dice")
+    SEMI = ("semi_mt", "semi_uamt", "semi_entmin")     # two student forwards per step: step(x_l, label_l, unlabeled=x_u)
     FUSED_REG = {"pce_tv": 1, "pce_ms": 2, "pce_entropy": 3}     # WSL_REG_* of wsl_head_reg_fwd_bwd (include/wsl_hip.h)
     REG_WEIGHT = {"pce_tv": 1e-2,        # train_weakly_supervised_pCE_TV_2D.py:113-114 (tv_loss on outputs_soft[1:])
                   "pce_ms": 1e-6,        # ..._pCE_MumfordShah_Loss_2D.py:102-103 (MumfordShah_Loss(image, softmax))
@@ -54,8 +71,9 @@ class TrainEngine:
     def __init__(self, net_type="unet_cct", in_chns=1, class_num=4, base_lr=0.01, max_iterations=60000, momentum=0.9,
                  weight_decay=1e-4, loss="ours_proposed", w_pse=0.5, crf_radius=5, crf_weight=0.1,
                  crf_desc=None, ignore_index=4, model=None, force_dp=False, conv_precision="f32", thr_iter=6000, thr_conf=0.8,
-                 s2l_alpha=0.2, period_iter=100, var_consistency=0.1, var_rampup=200.0):
-        if loss not in ("ours_proposed", "pce", "pce_gatedcrf", "mean_teacher", "ustm", "s2l", "pce_interintra") + self.REGULARISED:
+                 s2l_alpha=0.2, period_iter=100, var_consistency=0.1, var_rampup=200.0, consistency=0.1, consistency_rampup=200.0,
+                 ema_decay=0.99, teacher_update="ema"):
+        if loss not in ("ours_proposed", "pce", "pce_gatedcrf", "mean_teacher", "ustm", "s2l", "pce_interintra") + self.REGULARISED + self.SEMI:
             raise NotImplementedError(f"loss composition '{loss}'")
         # conv_precision: "f32" (default, the headline path) | "split_f16x3" (opt-in: networks/unet.py, include/wsl_hip.h)
         self.model = model if model is not None else net_factory(net_type, in_chns, class_num, conv_precision=conv_precision)
@@ -71,6 +89,10 @@ class TrainEngine:
             raise _lib.WslError("'s2l' is a single-decoder composition (unet, pnet)")
         if loss == "pce_interintra" and self.dual:
             raise _lib.WslError("'pce_interintra' is a single-decoder composition (unet, pnet)")
+        if loss in self.SEMI and self.dual:
+            raise _lib.WslError(f"'{loss}' is a single-decoder composition (unet, pnet)")
+        if teacher_update not in ("ema", "frozen"):
+            raise ValueError(f"teacher_update {teacher_update!r} (one of 'ema', 'frozen')")
         self.loss_kind, self.w_pse, self.ignore = loss, w_pse, ignore_index
         # inter/intra-class variance (..._pCE_Inter&Intra_Class_2D.py:62-70 --consistency / --consistency_rampup, :115 the ramp's argument)
         self.var_consistency, self.var_rampup, self._var_w, self._var_slot = var_consistency, var_rampup, 0.0, 4
@@ -107,6 +129,20 @@ class TrainEngine:
                 self.teacher._param_arena.copy_(self.model._param_arena)
                 self.teacher._buf_arena.copy_(self.model._buf_arena)
             self.tv_weight, self.cons_max, self.ema_decay = 1e-2, 0.1, 0.99
+        # semi-supervised trainers (train_mean_teacher_2D.py:60-66 --ema_decay / --consistency / --consistency_rampup, :73-75 the ramp)
+        self.consistency, self.consistency_rampup, self.teacher_update = consistency, consistency_rampup, teacher_update
+        self._semi_w, self._semi_thr, self._kept = 0.0, 0.0, None
+        if loss in ("semi_mt", "semi_uamt"):
+            self.teacher = net_factory(net_type, in_chns, class_num, conv_precision=self.model.conv_precision)
+            self.teacher.train()                          # the reference never puts the EMA model in eval()
+            with torch.no_grad():
+                self.teacher._param_arena.copy_(self.model._param_arena)
+                self.teacher._buf_arena.copy_(self.model._buf_arena)
+            self.ema_decay = ema_decay
+        if loss == "semi_uamt":
+            # measured (profiles/semi_bench.md): at the reference's batch of 6 + 6 the fused supervised head leaves this step 1.9 % slower than
+            # the chain against a spread of 0.1 % (1.0 % faster at 32 + 32) -- the one row of six that misses the condition for a fused default
+            self.fused_heads = False
 
     # ------------------------------------------------------------------ helpers
     def _tensors(self, N, H, W):
@@ -144,10 +180,11 @@ class TrainEngine:
                 dist.all_reduce(flat)
 
     # ------------------------------------------------------------------ one optimiser step
-    def step(self, x, label_u8, beta=0.5, noise=None, weight=None):
+    def step(self, x, label_u8, beta=0.5, noise=None, weight=None, unlabeled=None, masks=None):
         """One optimiser step: forward, loss, backward (+ gradient all-reduce), SGD (+EMA teacher), poly-LR update.
-        weight ('s2l'): the loader's [N,H,W,C] batch of the running prediction average; read from `thr_iter` on."""
-        self.forward_backward(x, label_u8, beta, noise, weight)
+        weight ('s2l'): the loader's [N,H,W,C] batch of the running prediction average; read from `thr_iter` on.
+        unlabeled ('semi_*'): the unlabeled image batch x_u (any N, the H x W of x); masks: see forward_backward."""
+        self.forward_backward(x, label_u8, beta, noise, weight, unlabeled, masks)
         self.optimizer_step()
 
     def _noisy(self, x, noise, reps=1):
@@ -303,8 +340,18 @@ class TrainEngine:
                 rt.ptr(lws), nl, rt.stream())
         rt.call("wsl_axpy", rt.ptr(t["dz1"]), rt.ptr(t["dzx"]), 1.0, N * C_ * HW, rt.stream())
 
-    def forward_backward(self, x, label_u8, beta=0.5, noise=None, weight=None):
-        """Everything up to (and including) the gradient all-reduce; flat_grads() then holds the SUM over ranks."""
+    def forward_backward(self, x, label_u8, beta=0.5, noise=None, weight=None, unlabeled=None, masks=None):
+        """Everything up to (and including) the gradient all-reduce; flat_grads() then holds the SUM over ranks.
+        'semi_*': x / label_u8 are the labeled half, `unlabeled` the unlabeled image batch; noise: None (drawn like the scripts) or
+        the teacher's input noise -- a tensor ('semi_mt') / a list of 1 + T//2 tensors ('semi_uamt': the teacher input's, then the
+        four double batches'); masks = (m_l, m_u) replays dropout masks for the two student forwards, each entry what the model's
+        set_dropout_masks takes (a tuple for several arguments)."""
+        if self.loss_kind in self.SEMI:
+            if unlabeled is None:
+                raise _lib.WslError(f"'{self.loss_kind}' needs step(x_l, label_l, unlabeled=x_u): the unlabeled image batch")
+            return self._semi_forward_backward(x, label_u8, unlabeled, noise, masks)
+        if unlabeled is not None or masks is not None:
+            raise _lib.WslError(f"unlabeled= / masks= belong to the semi-supervised compositions {self.SEMI}, not to '{self.loss_kind}'")
         m = self.model
         x = rt.f32c(x, "image batch")
         N, _, H, W = x.shape
@@ -348,6 +395,124 @@ class TrainEngine:
                     rt.stream())
         self._s2l_fused = self.loss_kind == "s2l" and self.it >= self.thr_iter
         self._finish_backward(x, t)
+
+    # ------------------------------------------------------------------ semi-supervised: two student forwards per step
+    def consistency_weight(self, it=None):
+        """w(t) of the 'semi_*' compositions: get_current_consistency_weight(iter_num // 300) (train_mean_teacher_2D.py:73-75, 164-165);
+        consistency_rampup = 0: the constant weight"""
+        from .utils.ramps import sigmoid_rampup
+        return self.consistency * sigmoid_rampup((self.it if it is None else it) // 300, self.consistency_rampup)
+
+    def uncertainty_threshold(self, it=None):
+        """(0.75 + 0.25 * sigmoid_rampup(iter_num, max_iterations)) * ln 2 (train_uncertainty_aware_mean_teacher_2D.py:184-185)"""
+        from .utils.ramps import sigmoid_rampup
+        return (0.75 + 0.25 * sigmoid_rampup(self.it if it is None else it, self.max_it)) * math.log(2.0)
+
+    def _set_masks(self, mk):
+        m = self.model
+        m.set_dropout_masks(*mk) if isinstance(mk, tuple) else m.set_dropout_masks(mk)
+
+    def _sup_head(self, z, label_u8, dz, t, N, C_, HW):
+        """0.5 * (CE(z, label) + DiceLoss(softmax(z), label)) of the labeled half: loss_out[0..3] = {sup, ce, dice, n_valid}"""
+        lo = self.loss_out
+        nl = rt.L().wsl_loss_ws_bytes(N, C_, HW)
+        lws = rt.workspace("loss", nl)
+        if self.fused_heads:
+            rt.call("wsl_sup_head_fwd_bwd", rt.ptr(z), rt.ptr(label_u8), self.ignore, 0.5, 0.5, 1.0, rt.ptr(lo), rt.ptr(dz), N, C_, HW,
+                    rt.ptr(lws), nl, rt.stream())
+            return
+        # the chain `ce_dice` runs: head (0.5 * CE), softmax, DiceLoss forward / backward, softmax backward, axpy; the Dice value lands in
+        # loss_out[4] and moves to slot 2 (the head's unused `pse`), so both routes leave the same layout
+        if "dice" not in t:
+            t["dice"] = (torch.empty(3 * C_, dtype=torch.float32, device=z.device), torch.full((1,), 0.5, dtype=torch.float32, device=z.device))
+        sums, gout = t["dice"]
+        rt.call("wsl_head_fwd_bwd", rt.ptr(z), None, rt.ptr(label_u8), self.ignore, 0.0, 0.0, 0.5, rt.ptr(lo), None, rt.ptr(dz), None,
+                N, C_, HW, rt.ptr(lws), nl, rt.stream())
+        rt.call("wsl_softmax_fwd", rt.ptr(z), rt.ptr(t["s"]), N, C_, HW, rt.stream())
+        rt.call("wsl_pdice_fwd", rt.ptr(t["s"]), rt.ptr(label_u8), 0, -1, rt.ptr(lo[4:]), rt.ptr(sums), N, C_, HW, rt.ptr(lws), nl, rt.stream())
+        rt.call("wsl_pdice_bwd", rt.ptr(t["s"]), rt.ptr(label_u8), 0, -1, rt.ptr(sums), rt.ptr(gout), rt.ptr(t["ds"]), N, C_, HW, rt.stream())
+        rt.call("wsl_softmax_bwd", rt.ptr(t["s"]), rt.ptr(t["ds"]), rt.ptr(t["dzx"]), N, C_, HW, rt.stream())
+        rt.call("wsl_axpy", rt.ptr(dz), rt.ptr(t["dzx"]), 1.0, N * C_ * HW, rt.stream())
+        lo[2:3].copy_(lo[4:5])      # (slot 0 holds the head's plain CE on this route: losses() forms sup from ce and dice on both)
+
+    def _semi_tensors(self, N, H, W, which):
+        key = ("semi", which, N, H, W)
+        if key not in self._bufs:
+            dev, C_ = rt.device(), self.model.class_num
+            mk = lambda: torch.empty((N, C_, H, W), dtype=torch.float32, device=dev)  # noqa: E731
+            t = {"dz": mk(), "mk": mk}
+            if which == "u" and self.loss_kind == "semi_uamt":
+                t["pm"] = mk()
+            self._bufs[key] = t
+        t = self._bufs[key]
+        chain = not self.fused_heads and (which == "l" or self.loss_kind == "semi_entmin")
+        if chain and "s" not in t:                        # the chains of calls keep softmax(z) and its gradient
+            t["s"], t["ds"], t["dzx"] = t["mk"](), t["mk"](), t["mk"]()
+        return t
+
+    def _semi_forward_backward(self, x, label_u8, xu, noise, masks):
+        """forward(x_l) -> supervised head -> backward -> keep the arena; forward(x_u) -> unsupervised head -> backward -> add the kept
+        arena.  loss_out: [0..3] = {sup, ce, dice, n_valid}, [4] = the raw unsupervised term, [5] = sum(mask) ('semi_uamt')."""
+        m, kind = self.model, self.loss_kind
+        x, xu = rt.f32c(x, "image batch"), rt.f32c(xu, "unlabeled image batch")
+        if xu.dim() != 4 or x.dim() != 4 or tuple(xu.shape[1:]) != tuple(x.shape[1:]):
+            raise _lib.WslError(f"labeled batch {tuple(x.shape)} and unlabeled batch {tuple(xu.shape)} may differ in N only")
+        if masks is not None and len(masks) != 2:
+            raise _lib.WslError("masks = (m_l, m_u): one entry per student forward")
+        N, _, H, W = x.shape
+        Nu, HW, C_ = xu.shape[0], H * W, m.class_num
+        tl, tu = self._semi_tensors(N, H, W, "l"), self._semi_tensors(Nu, H, W, "u")
+        lo = self.loss_out
+        m.train()
+        self._patch = (H, W)
+        n0 = noise if (noise is None or torch.is_tensor(noise)) else noise[0]
+        if kind == "semi_uamt" and noise is not None and (torch.is_tensor(noise) or len(noise) != 5):
+            raise _lib.WslError("'semi_uamt' replays 1 + T//2 = 5 noise tensors: the teacher input's, then the four double batches'")
+        if self.teacher is not None:
+            self._start_teacher(xu, n0)
+        try:
+            # ---- the labeled half
+            if masks is not None:
+                self._set_masks(masks[0])
+            z_l = m._run_forward(x, keep_for_backward=True)[0]
+            self._sup_head(z_l, label_u8, tl["dz"], tl, N, C_, HW)
+            m._run_backward(x, [tl["dz"], None], phase=0)
+            flat_g = m.flat_grads()
+            if self._kept is None or self._kept.numel() != flat_g.numel() or self._kept.device != flat_g.device:
+                self._kept = torch.empty_like(flat_g)
+            self._kept.copy_(flat_g)                      # wsl_net_backward OVERWRITES the arena
+            # ---- the unlabeled half
+            if masks is not None:
+                self._set_masks(masks[1])
+            z_u = m._run_forward(xu, keep_for_backward=True)[0]
+        finally:
+            if masks is not None:
+                m.set_dropout_masks(None)
+        w = self._semi_w = self.consistency_weight()
+        nl = rt.L().wsl_loss_ws_bytes(Nu, C_, HW)
+        lws = rt.workspace("loss", nl)
+        if kind == "semi_entmin":
+            if self.fused_heads:
+                rt.call("wsl_entropy_logits_fwd_bwd", rt.ptr(z_u), rt.ptr(lo[4:]), rt.ptr(tu["dz"]), w, Nu, C_, HW, 4, rt.ptr(lws), nl, rt.stream())
+            else:
+                rt.call("wsl_softmax_fwd", rt.ptr(z_u), rt.ptr(tu["s"]), Nu, C_, HW, rt.stream())
+                rt.call("wsl_entropy_fwd_bwd", rt.ptr(tu["s"]), rt.ptr(lo[4:]), rt.ptr(tu["ds"]), w, Nu, C_, HW, 4, rt.ptr(lws), nl, rt.stream())
+                rt.call("wsl_softmax_bwd", rt.ptr(tu["s"]), rt.ptr(tu["ds"]), rt.ptr(tu["dz"]), Nu, C_, HW, rt.stream())
+        elif kind == "semi_mt":
+            zt = self._teacher_logits(xu, n0)             # usually already in flight on the side stream
+            rt.call("wsl_softmax_mse_fwd_bwd", rt.ptr(z_u), rt.ptr(zt), rt.ptr(lo[4:]), rt.ptr(tu["dz"]), w, Nu, C_, HW, rt.ptr(lws), nl, rt.stream())
+        else:
+            T_ = 8
+            zt = self._teacher_logits(xu, n0)             # joins the side stream: the passes below reuse the teacher's workspace
+            with torch.no_grad():
+                for i in range(T_ // 2):                  # T stochastic passes, two per double batch (x_u.repeat(2, 1, 1, 1))
+                    z2 = self.teacher._run_forward(self._noisy(xu, noise[1 + i] if noise is not None else None, reps=2))[0]
+                    for h in range(2):
+                        rt.call("wsl_softmax_accum", rt.ptr(z2[h * Nu:]), rt.ptr(tu["pm"]), 1.0 / T_, int(i == 0 and h == 0), Nu, C_, HW, rt.stream())
+            thr = self._semi_thr = self.uncertainty_threshold()
+            rt.call("wsl_ustm_consistency_fwd_bwd", rt.ptr(z_u), rt.ptr(zt), rt.ptr(tu["pm"]), float(thr), rt.ptr(lo[4:]), rt.ptr(tu["dz"]), w,
+                    Nu, C_, HW, rt.ptr(lws), nl, rt.stream())
+        self._finish_backward(xu, {"dz1": tu["dz"], "dz2": None}, kept=self._kept)
 
     # ------------------------------------------------------------------ Scribble2Label: the running prediction average
     def ensemble_due(self):
@@ -412,15 +577,22 @@ class TrainEngine:
                 m.set_dropout_masks(None)
             m.train(was_training)
 
-    def _finish_backward(self, x, t):
+    def _finish_backward(self, x, t, kept=None):
+        """kept ('semi_*'): the gradient arena of the step's FIRST backward, added to this one's before each bucket leaves (the first
+        backward never all-reduces); the elementwise additions are the same with and without data parallelism"""
         m = self.model
         g = [t["dz1"], t["dz2"]]
         flat_g = m.flat_grads()
+        ne = m.n_enc_param
         if self.dp:
             m._run_backward(x, g, phase=1)
-            self._allreduce(flat_g[m.n_enc_param:])
+            if kept is not None:
+                rt.call("wsl_axpy", rt.ptr(flat_g[ne:]), rt.ptr(kept[ne:]), 1.0, flat_g.numel() - ne, rt.stream())
+            self._allreduce(flat_g[ne:])
             m._run_backward(x, g, phase=2)
-            self._allreduce(flat_g[:m.n_enc_param])
+            if kept is not None:
+                rt.call("wsl_axpy", rt.ptr(flat_g[:ne]), rt.ptr(kept[:ne]), 1.0, ne, rt.stream())
+            self._allreduce(flat_g[:ne])
             if self.comm is not None:
                 cur = torch.cuda.current_stream()
                 if self._diag is not None:
@@ -433,6 +605,8 @@ class TrainEngine:
                     cur.wait_stream(self.comm)
         else:
             m._run_backward(x, g, phase=0)
+            if kept is not None:
+                rt.call("wsl_axpy", rt.ptr(flat_g), rt.ptr(kept), 1.0, flat_g.numel(), rt.stream())
 
     def comm_diag(self, on):
         """on=True: start timing how long the main stream sits blocked on the all-reduce stream at the end of every backward;
@@ -460,7 +634,9 @@ class TrainEngine:
     def optimizer_step(self):
         m = self.model
         ema, alpha = None, 0.0
-        if self.teacher is not None:      # update_ema_variables(model, ema_model, 0.99, iter_num), iter before increment
+        if self.teacher is not None and not (self.loss_kind in self.SEMI and self.teacher_update == "frozen"):
+            # update_ema_variables(model, ema_model, 0.99, iter_num), iter before increment ("frozen": the call the reference's two
+            # mean-teacher scripts never make)
             ema, alpha = self.teacher._param_arena, min(1.0 - 1.0 / (self.it + 1), self.ema_decay)
         rt.call("wsl_sgd_step", rt.ptr(m._param_arena), rt.ptr(m._grad_arena), rt.ptr(self.mom), self.n, float(self.lr),
                 self.mu, self.wd, int(self.it == 0), 1.0 / self.world, rt.ptr(ema), alpha, rt.stream())
@@ -468,10 +644,17 @@ class TrainEngine:
         self.it += 1
 
     def losses(self):
-        """{loss, ce, pse|crf, n_valid} of the last step (host sync)."""
+        """{loss, ce, pse|crf, n_valid} of the last step (host sync); 'semi_*': {loss, ce, dice, sup, cons, w, n_valid} with
+        sup = 0.5 * (ce + dice), cons the raw unsupervised term and loss = sup + w * cons ('semi_uamt' adds n_certain, threshold)."""
         o = self.loss_out.tolist()
         if self.loss_kind == "pce_gatedcrf":
             return {"loss": o[1] + self.crf_weight * o[4], "ce": o[1], "crf": o[4], "n_valid": o[3]}
+        if self.loss_kind in self.SEMI:        # cons is the raw (unweighted) unsupervised term, w the weight the step used
+            sup = 0.5 * (o[1] + o[2])
+            d = {"loss": sup + self._semi_w * o[4], "ce": o[1], "dice": o[2], "sup": sup, "cons": o[4], "w": self._semi_w, "n_valid": o[3]}
+            if self.loss_kind == "semi_uamt":
+                d["n_certain"], d["threshold"] = o[5], self._semi_thr
+            return d
         if self.loss_kind == "ce_dice":
             return {"loss": 0.5 * (o[1] + o[4]), "ce": o[1], "dice": o[4], "n_valid": o[3]}
         if self.loss_kind in self.REGULARISED:  # reg is the raw (unweighted) regulariser
