@@ -14,6 +14,9 @@ train_entropy_minimization_2D.py (code/train_semi.sh): two datasets (labeled_typ
 --batch_size // 2 each, zip(cycle(labeled), unlabeled); the student runs on both halves, 0.5 * (CE + Dice) on the labeled one and
 w(t) * the consistency / entropy term on the unlabeled one, w(t) = --consistency * sigmoid_rampup(iteration // 300, --consistency_rampup).
 --teacher_update frozen is the reference's scripts to the letter (they never call update_ema_variables); the default ema is the method.
+--loss semi_dan is the flow of code/train_deep_adversarial_network_2D.py on the same two datasets and loaders: 0.5 * (CE + Dice) on the
+labeled half plus w(t) * CE(DAN(softmax(z_u), x_u), 1) on the unlabeled one, w(t) = --consistency * sigmoid_rampup(iteration // 150,
+--consistency_rampup), then the adversary's own Adam step (FCDiscriminator, --dan_ndf filters; --dan_pool 7 needs a 224 .. 335 patch).
 (train_partially_fully_supervised.py is --loss ce_dice --sup_type label --labeled_type labeled.)
 
     python examples/train_acdc_scribble.py --root_path <.../data/ACDC> --fold fold1 --max_iterations 60000
@@ -46,15 +49,20 @@ def main(argv=None):
     ap.add_argument("--model", default=None, choices=["unet_cct", "unet", "pnet"], help="default: unet_cct, and unet for --loss s2l / "
                     "pce_interintra (single-decoder compositions: unet or pnet)")
     ap.add_argument("--loss", default="ours_proposed", choices=["ours_proposed", "pce", "pce_gatedcrf", "pce_tv", "pce_ms", "pce_entropy", "ce_dice", "mean_teacher", "ustm", "s2l", "pce_interintra",
-                                                                     "semi_mt", "semi_uamt", "semi_entmin"])
+                                                                     "semi_mt", "semi_uamt", "semi_entmin", "semi_dan"])
     # inter/intra-class variance (train_weakly_supervised_pCE_Inter&Intra_Class_2D.py:62-65)
     ap.add_argument("--consistency", type=float, default=0.1, help="pce_interintra / semi_*: the weight's plateau")
     ap.add_argument("--consistency_rampup", type=float, default=200.0, help="pce_interintra / semi_*: length of the sigmoid ramp in units of "
-                    "150 (semi_*: 300) iterations (0 = constant weight)")
+                    "150 (semi_mt / semi_uamt / semi_entmin: 300) iterations (0 = constant weight)")
     # semi-supervised trainers (train_mean_teacher_2D.py:60-66)
     ap.add_argument("--ema_decay", type=float, default=0.99)
     ap.add_argument("--teacher_update", default="ema", choices=["ema", "frozen"], help="semi_mt / semi_uamt: 'frozen' = the reference's "
                     "scripts literally (update_ema_variables is defined and never called: the teacher keeps its initial weights)")
+    # the adversary of semi_dan (train_deep_adversarial_network_2D.py:117-123)
+    ap.add_argument("--dan_lr", type=float, default=1e-4)
+    ap.add_argument("--dan_ndf", type=int, default=64)
+    ap.add_argument("--dan_pool", type=int, default=7, help="semi_dan: window of the adversary's AvgPool2d (the reference's 7 fits patches of "
+                    "224 .. 335; the pooled map must have 4 positions)")
     # Scribble2Label (train_s2l.py:62-65)
     ap.add_argument("--period_iter", type=int, default=100)
     ap.add_argument("--thr_iter", type=int, default=6000)
@@ -122,7 +130,8 @@ def main(argv=None):
     eng = TrainEngine(args.model, 1, args.num_classes, base_lr=args.base_lr, max_iterations=args.max_iterations,
                       loss=args.loss, thr_iter=args.thr_iter, thr_conf=args.thr_conf, s2l_alpha=args.alpha, period_iter=args.period_iter,
                       var_consistency=args.consistency, var_rampup=args.consistency_rampup, consistency=args.consistency,
-                      consistency_rampup=args.consistency_rampup, ema_decay=args.ema_decay, teacher_update=args.teacher_update)
+                      consistency_rampup=args.consistency_rampup, ema_decay=args.ema_decay, teacher_update=args.teacher_update,
+                      dan_lr=args.dan_lr, dan_ndf=args.dan_ndf, dan_pool=args.dan_pool)
     if args.resume:
         eng.model.load_state_dict(torch.load(args.resume, map_location="cpu"))
     if args.snapshot_path and rank == 0:

@@ -651,6 +651,69 @@ int wsl_upblock_t_forward(const WslUpBlockDesc* d, const float* params, float* b
 int wsl_upblock_t_backward(const WslUpBlockDesc* d, const float* params, const float* x1, const float* x2, const uint8_t* emask,
                            const float* dout, float* grads, float* dx1, float* dx2, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------ DAN: the adversary
+ * FCDiscriminator(num_classes, ndf, n_channel) (ref: networks/discriminator.py; trainer train_deep_adversarial_network_2D.py):
+ *   x = conv0(map) + conv1(image)  (no activation) -> conv2 -> LeakyReLU(0.2) -> Dropout2d(0.5) -> conv3 -> LeakyReLU -> Dropout2d ->
+ *   conv4 -> LeakyReLU -> AvgPool2d(pool) -> view(N, -1) -> Linear(ndf*32, 2);  every conv is 4x4, stride 2, padding 1.
+ * All kernels: fp32 in and out, no atomics (two calls give the same bits), any N, Ci, Co >= 1 and H, W >= 2 (Ho = H / 2, Wo = W / 2;
+ * ragged tiles and channel tails are masked; alignment only selects vector loads / stores).  Weights are nn.Conv2d's [Co][Ci][4][4]. */
+#define WSL_DAN_LEAKY_SLOPE 0.2f
+/* y [N][Co][H/2][W/2] = conv(a', wa) + conv(xb, wb) + ba + bb, a' = xa, LeakyReLU(0.2)(xa) if act, times cmask[n][c] if cmask
+ * ([N][Ca] Dropout2d multipliers): the PRE-activation is stored, the consumer's loader applies activation and mask.  Cb = 0: one
+ * source (xb, wb, bb ignored); ba / bb may be NULL.  WSL_EINVAL, nothing written: NULL xa / wa / y, a second source without data or
+ * weights, N, Ca, Co < 1, H or W < 2. */
+int wsl_conv4s2_fwd(const float* xa, int Ca, const float* xb, int Cb, int act, const float* cmask, const float* wa, const float* wb,
+                    const float* ba, const float* bb, float* y, int N, int H, int W, int Co, void* stream);
+/* dx [N][Ci][H][W] = conv^T(dy, w), dy = g * cmask[n][co] * LeakyReLU'(z): g [N][Co][H/2][W/2] is the gradient that reached the layer's
+ * (activated, masked) output, z its saved pre-activation (NULL: g already is the gradient of the pre-activation), cmask NULL = none.
+ * Four stride-1 2x2-tap convolutions, one per (row, column) parity of dx; every element of dx is written once (rows / columns no
+ * output touches get 0).  WSL_EINVAL, nothing written: NULL g / w / dx, N, Ci, Co < 1, H or W < 2. */
+int wsl_conv4s2_dgrad(const float* g, const float* z, const float* cmask, const float* w, float* dx, int N, int Ci, int H, int W, int Co,
+                      void* stream);
+/* dw [Co][Ci][4][4] (and db [Co] unless NULL) of one source x [N][Ci][H][W] (LeakyReLU if act, times cmask_in) against the same dy as
+ * wsl_conv4s2_dgrad.  Partials [nsplit][16][Co][Ci] + [nsplit][Co] in ws, reduced in a fixed order.  A merged layer takes one call per
+ * source (dw0, dw1) and gets db0 = db1.  WSL_EINVAL: NULL x / g / dw / ws, bad shape; WSL_EWORKSPACE: ws_bytes below the query. */
+size_t wsl_conv4s2_wgrad_ws_bytes(int N, int H, int W, int Ci, int Co);
+int wsl_conv4s2_wgrad(const float* x, int act, const float* cmask_in, const float* g, const float* z, const float* cmask_out, float* dw,
+                      float* db, int N, int Ci, int H, int W, int Co, void* ws, size_t ws_bytes, void* stream);
+/* The head on conv4's pre-activation z [N][C][H][W]: LeakyReLU -> AvgPool2d(pool) (stride pool, floor) -> flatten (index c*4 + y*wp + x)
+ * -> Linear Wc [2][4C], bc [2] -> cross entropy against target[n] in {0, 1}, mean over N.  loss (1 float), logits [N][2]; dz (unless
+ * NULL) = gscale * dloss/dz; dW / db (both or neither; need dz) = gscale * the classifier's gradients.
+ * WSL_EINVAL, nothing written: (H / pool) * (W / pool) != 4, pool < 1, a NULL required pointer. */
+size_t wsl_dan_head_ws_bytes(int N, int C);
+int wsl_dan_head_fwd_bwd(const float* z, const int32_t* target, const float* Wc, const float* bc, int pool, float gscale, float* loss,
+                         float* logits, float* dz, float* dW, float* db, int N, int C, int H, int W, void* ws, size_t ws_bytes,
+                         void* stream);
+/* torch.optim.Adam (no amsgrad, no weight decay) over a flat arena: g = grad * grad_scale; m += (1 - beta1)(g - m);
+ * v = beta2 v + (1 - beta2) g^2; p -= lr / (1 - beta1^step) * m / (sqrt(v) / sqrt(1 - beta2^step) + eps).  step counts from 1; the
+ * bias corrections are computed on the host in double. */
+int wsl_adam_step(float* p, const float* grad, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, int step,
+                  float grad_scale, void* stream);
+/* The network over flat arenas; entries in the reference's state_dict order: conv0.{weight,bias}, conv1, conv2, conv3, conv4,
+ * classifier.  The layout queries (_num_entries / _entry / _param_count / _buffer_count) read the four channel fields only. */
+typedef struct WslDanDesc {
+  int32_t num_classes, n_channel, ndf, pool;   /* pool: AvgPool2d's window; the reference's is 7 */
+  int32_t N, H, W, _pad;                       /* (H/16/pool) * (W/16/pool) must be 4 */
+} WslDanDesc;
+#define WSL_DAN_GRAD_MAP 1      /* wsl_dan_backward: gradient with respect to `map` (never the image) */
+#define WSL_DAN_GRAD_PARAMS 2   /* ... and / or the parameter gradients (the whole gradient arena is overwritten) */
+int wsl_dan_num_entries(const WslDanDesc* d);
+int wsl_dan_entry(const WslDanDesc* d, int i, WslNetEntry* out);
+int64_t wsl_dan_param_count(const WslDanDesc* d);
+int64_t wsl_dan_buffer_count(const WslDanDesc* d);   /* 0: the module has no buffers */
+size_t wsl_dan_ws_bytes(const WslDanDesc* d);        /* 0 (and wsl_last_error) for a shape the head refuses */
+/* map [N][num_classes][H][W], feature [N][n_channel][H][W] -> logits [N][2].  training: cmasks[2] = the Dropout2d multipliers (0 or 2)
+ * [N][2 ndf] after conv2 and [N][4 ndf] after conv3; eval: ignored.  target != NULL: also the cross entropy (loss, 1 float) and its
+ * gradient scaled by gscale, kept in ws for wsl_dan_backward(dlogits = NULL).  Keeps what the backward needs in ws.
+ * WSL_EINVAL, nothing written: a pooled map without 4 positions, a level with H or W < 2, a NULL required pointer. */
+int wsl_dan_forward(const WslDanDesc* d, const float* params, const float* map, const float* feature, const float* const* cmasks,
+                    int training, const int32_t* target, float gscale, float* logits, float* loss, void* ws, size_t ws_bytes, void* stream);
+/* Backward of the last forward held in ws.  dlogits [N][2] or NULL (the cross-entropy gradient the forward kept); cmasks as the forward
+ * saw them (NULL after an eval forward); flags: WSL_DAN_GRAD_MAP -> dmap [N][num_classes][H][W], WSL_DAN_GRAD_PARAMS -> grads (laid out
+ * as params).  Without _PARAMS no weight gradient is computed; without _MAP conv0's data gradient is skipped. */
+int wsl_dan_backward(const WslDanDesc* d, const float* params, const float* map, const float* feature, const float* const* cmasks,
+                     const float* dlogits, int flags, float* dmap, float* grads, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

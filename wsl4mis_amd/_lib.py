@@ -50,6 +50,11 @@ class WslPNetDesc(C.Structure):
                 ("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32)]
 
 
+class WslDanDesc(C.Structure):
+    _fields_ = [("num_classes", C.c_int32), ("n_channel", C.c_int32), ("ndf", C.c_int32), ("pool", C.c_int32),
+                ("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("_pad", C.c_int32)]
+
+
 class WslNetEntry(C.Structure):
     _fields_ = [("name", C.c_char * 96), ("kind", C.c_int32), ("ndim", C.c_int32), ("shape", C.c_int64 * 4),
                 ("offset", C.c_int64)]
@@ -75,6 +80,7 @@ i32, i64, f32, f64, sz = C.c_int, C.c_int64, C.c_float, C.c_double, C.c_size_t
 PS, PD, PE = C.POINTER(WslSrc), C.POINTER(WslNetDesc), C.POINTER(WslNetEntry)
 PP = C.POINTER(c_fp)
 PQ = C.POINTER(WslPNetDesc)
+PDAN = C.POINTER(WslDanDesc)
 
 _PROTOS = {
     "wsl_version": (i32, []),
@@ -195,6 +201,20 @@ _PROTOS = {
     "wsl_pnet_ws_bytes": (sz, [PQ]),
     "wsl_pnet_forward": (i32, [PQ, c_fp, c_fp, c_fp, c_fp, PP, i32, c_fp, c_fp, sz, c_fp]),
     "wsl_pnet_backward": (i32, [PQ, c_fp, c_fp, PP, c_fp, c_fp, c_fp, sz, i32, c_fp]),
+    "wsl_conv4s2_fwd": (i32, [c_fp, i32, c_fp, i32, i32, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, i32, i32, i32, i32, c_fp]),
+    "wsl_conv4s2_dgrad": (i32, [c_fp, c_fp, c_fp, c_fp, c_fp, i32, i32, i32, i32, i32, c_fp]),
+    "wsl_conv4s2_wgrad_ws_bytes": (sz, [i32, i32, i32, i32, i32]),
+    "wsl_conv4s2_wgrad": (i32, [c_fp, i32, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, i32, i32, i32, i32, i32, c_fp, sz, c_fp]),
+    "wsl_dan_head_ws_bytes": (sz, [i32, i32]),
+    "wsl_dan_head_fwd_bwd": (i32, [c_fp, c_fp, c_fp, c_fp, i32, f32, c_fp, c_fp, c_fp, c_fp, c_fp, i32, i32, i32, i32, c_fp, sz, c_fp]),
+    "wsl_adam_step": (i32, [c_fp, c_fp, c_fp, c_fp, i64, f32, f32, f32, f32, i32, f32, c_fp]),
+    "wsl_dan_num_entries": (i32, [PDAN]),
+    "wsl_dan_entry": (i32, [PDAN, i32, PE]),
+    "wsl_dan_param_count": (i64, [PDAN]),
+    "wsl_dan_buffer_count": (i64, [PDAN]),
+    "wsl_dan_ws_bytes": (sz, [PDAN]),
+    "wsl_dan_forward": (i32, [PDAN, c_fp, c_fp, c_fp, PP, i32, c_fp, f32, c_fp, c_fp, c_fp, sz, c_fp]),
+    "wsl_dan_backward": (i32, [PDAN, c_fp, c_fp, c_fp, PP, c_fp, i32, c_fp, c_fp, c_fp, sz, c_fp]),
     "wsl_net_num_entries": (i32, [PD]),
     "wsl_net_entry": (i32, [PD, i32, PE]),
     "wsl_net_param_count": (i64, [PD]),

@@ -39,6 +39,14 @@ Steps reproduced (reference file:line, all under code/):
                     teacher keeps its initial weights for the whole run.  "frozen" reproduces that literally (a step leaves the
                     teacher's parameter arena bit-unchanged); "ema" (default) places the call as train_weakly_supervised_ustm_2D.py:163
                     does, alpha = min(1 - 1 / (it + 1), ema_decay), which is what the method is
+  'semi_dan'        train_deep_adversarial_network_2D.py:135-184 (unet | pnet): the same two student forwards, with
+                    U = CE(DAN(softmax(z_u), x_u), t_u), t_u[i] = 1 if i < N_l else 0, DAN = networks/discriminator.py FCDiscriminator in
+                    eval mode, and w(t) = consistency * sigmoid_rampup(it // 150, consistency_rampup) -- 150, not 300.  The adversary's
+                    loss is differentiated into softmax(z_u) (wsl_dan_backward, data gradient only: the generator update needs none
+                    of its weight gradients), then through wsl_softmax_bwd into the student.  After the SGD step,
+                    discriminator_step(x_l, x_u): two EVAL forwards of the student (updated weights and running statistics, no
+                    gradient), softmax into one (N_l + N_u) batch, the adversary in train mode (Dropout2d drawn or replayed),
+                    CE against [1] * N_l + [0] * N_u, parameter gradients only, Adam(dan_lr, dan_betas) (wsl_adam_step)
 Optimiser: SGD(lr, momentum 0.9, wd 1e-4) with the poly schedule applied one step late (ours_proposed.py:126-132).
 
 Data parallel (DDP-equivalent semantics): one process per GPU, per-rank BatchNorm statistics and loss
@@ -60,7 +68,7 @@ from .networks.net_factory import net_factory
 class TrainEngine:
     # pCE + weight * regulariser(softmax(outputs)) of the single-branch scripts: (weight, reference lines)
     REGULARISED = ("pce_tv", "pce_ms", "pce_entropy", "ce_dice")
-    SEMI = ("semi_mt", "semi_uamt", "semi_entmin")     # two student forwards per step: step(x_l, label_l, unlabeled=x_u)
+    SEMI = ("semi_mt", "semi_uamt", "semi_entmin", "semi_dan")     # two student forwards per step: step(x_l, label_l, unlabeled=x_u)
     FUSED_REG = {"pce_tv": 1, "pce_ms": 2, "pce_entropy": 3}     # WSL_REG_* of wsl_head_reg_fwd_bwd (include/wsl_hip.h)
     REG_WEIGHT = {"pce_tv": 1e-2,        # train_weakly_supervised_pCE_TV_2D.py:113-114 (tv_loss on outputs_soft[1:])
                   "pce_ms": 1e-6,        # ..._pCE_MumfordShah_Loss_2D.py:102-103 (MumfordShah_Loss(image, softmax))
@@ -72,7 +80,7 @@ class TrainEngine:
                  weight_decay=1e-4, loss="ours_proposed", w_pse=0.5, crf_radius=5, crf_weight=0.1,
                  crf_desc=None, ignore_index=4, model=None, force_dp=False, conv_precision="f32", thr_iter=6000, thr_conf=0.8,
                  s2l_alpha=0.2, period_iter=100, var_consistency=0.1, var_rampup=200.0, consistency=0.1, consistency_rampup=200.0,
-                 ema_decay=0.99, teacher_update="ema"):
+                 ema_decay=0.99, teacher_update="ema", dan_lr=1e-4, dan_betas=(0.9, 0.99), dan_ndf=64, dan_pool=7):
         if loss not in ("ours_proposed", "pce", "pce_gatedcrf", "mean_teacher", "ustm", "s2l", "pce_interintra") + self.REGULARISED + self.SEMI:
             raise NotImplementedError(f"loss composition '{loss}'")
         # conv_precision: "f32" (default, the headline path) | "split_f16x3" (opt-in: networks/unet.py, include/wsl_hip.h)
@@ -139,6 +147,17 @@ class TrainEngine:
                 self.teacher._param_arena.copy_(self.model._param_arena)
                 self.teacher._buf_arena.copy_(self.model._buf_arena)
             self.ema_decay = ema_decay
+        self.discriminator = None
+        if loss == "semi_dan":
+            from .networks.discriminator import FCDiscriminator
+            # (train_deep_adversarial_network_2D.py:117-123: FCDiscriminator(num_classes, n_channel = the image's), Adam(1e-4, (0.9, 0.99)))
+            self.discriminator = D = FCDiscriminator(class_num, dan_ndf, in_chns, pool=dan_pool)
+            self.dan_lr, self.dan_betas, self.dan_eps, self.dan_it = float(dan_lr), (float(dan_betas[0]), float(dan_betas[1])), 1e-8, 0
+            self.dan_m = torch.zeros(D.n_param + 64, dtype=torch.float32, device=dev)
+            self.dan_v = torch.zeros(D.n_param + 64, dtype=torch.float32, device=dev)
+            self._dan_targets = {}
+            if self.world > 1:
+                dist.broadcast(D._param_arena, src=0)
         if loss == "semi_uamt":
             # measured (profiles/semi_bench.md): at the reference's batch of 6 + 6 the fused supervised head leaves this step 1.9 % slower than
             # the chain against a spread of 0.1 % (1.0 % faster at 32 + 32) -- the one row of six that misses the condition for a fused default
@@ -180,12 +199,15 @@ class TrainEngine:
                 dist.all_reduce(flat)
 
     # ------------------------------------------------------------------ one optimiser step
-    def step(self, x, label_u8, beta=0.5, noise=None, weight=None, unlabeled=None, masks=None):
+    def step(self, x, label_u8, beta=0.5, noise=None, weight=None, unlabeled=None, masks=None, dan_masks=None):
         """One optimiser step: forward, loss, backward (+ gradient all-reduce), SGD (+EMA teacher), poly-LR update.
         weight ('s2l'): the loader's [N,H,W,C] batch of the running prediction average; read from `thr_iter` on.
-        unlabeled ('semi_*'): the unlabeled image batch x_u (any N, the H x W of x); masks: see forward_backward."""
+        unlabeled ('semi_*'): the unlabeled image batch x_u (any N, the H x W of x); masks: see forward_backward.
+        'semi_dan': then the discriminator's update (discriminator_step; dan_masks replays its two Dropout2d multipliers)."""
         self.forward_backward(x, label_u8, beta, noise, weight, unlabeled, masks)
         self.optimizer_step()
+        if self.loss_kind == "semi_dan":
+            self.discriminator_step(x, unlabeled, dan_masks)
 
     def _noisy(self, x, noise, reps=1):
         """x (repeated `reps` times along the batch) + clamp(randn * 0.1, +-0.2) in one library launch (ustm_2D.py:125-127,
@@ -398,10 +420,11 @@ class TrainEngine:
 
     # ------------------------------------------------------------------ semi-supervised: two student forwards per step
     def consistency_weight(self, it=None):
-        """w(t) of the 'semi_*' compositions: get_current_consistency_weight(iter_num // 300) (train_mean_teacher_2D.py:73-75, 164-165);
-        consistency_rampup = 0: the constant weight"""
+        """w(t) of the 'semi_*' compositions: get_current_consistency_weight(iter_num // 300) (train_mean_teacher_2D.py:73-75, 164-165)
+        -- iter_num // 150 for 'semi_dan' (train_deep_adversarial_network_2D.py:153); consistency_rampup = 0: the constant weight"""
         from .utils.ramps import sigmoid_rampup
-        return self.consistency * sigmoid_rampup((self.it if it is None else it) // 300, self.consistency_rampup)
+        div = 150 if self.loss_kind == "semi_dan" else 300
+        return self.consistency * sigmoid_rampup((self.it if it is None else it) // div, self.consistency_rampup)
 
     def uncertainty_threshold(self, it=None):
         """(0.75 + 0.25 * sigmoid_rampup(iter_num, max_iterations)) * ln 2 (train_uncertainty_aware_mean_teacher_2D.py:184-185)"""
@@ -443,6 +466,8 @@ class TrainEngine:
             t = {"dz": mk(), "mk": mk}
             if which == "u" and self.loss_kind == "semi_uamt":
                 t["pm"] = mk()
+            if which == "u" and self.loss_kind == "semi_dan":
+                t["s"] = mk()                             # softmax(z_u): the adversary's `map`
             self._bufs[key] = t
         t = self._bufs[key]
         chain = not self.fused_heads and (which == "l" or self.loss_kind == "semi_entmin")
@@ -498,6 +523,16 @@ class TrainEngine:
                 rt.call("wsl_softmax_fwd", rt.ptr(z_u), rt.ptr(tu["s"]), Nu, C_, HW, rt.stream())
                 rt.call("wsl_entropy_fwd_bwd", rt.ptr(tu["s"]), rt.ptr(lo[4:]), rt.ptr(tu["ds"]), w, Nu, C_, HW, 4, rt.ptr(lws), nl, rt.stream())
                 rt.call("wsl_softmax_bwd", rt.ptr(tu["s"]), rt.ptr(tu["ds"]), rt.ptr(tu["dz"]), Nu, C_, HW, rt.stream())
+        elif kind == "semi_dan":
+            # w * CE(DAN(softmax(z_u), x_u), t_u): the adversary in eval mode, its loss differentiated into softmax(z_u) only (no weight
+            # gradient: the reference discards them), the weight w folded into the head's gradient scale
+            D = self.discriminator
+            D.eval()
+            rt.call("wsl_softmax_fwd", rt.ptr(z_u), rt.ptr(tu["s"]), Nu, C_, HW, rt.stream())
+            _, adv = D._run_forward(tu["s"], xu, keep_for_backward=True, target=self._dan_target(N, Nu, False), gscale=float(w))
+            ds = D._run_backward(tu["s"], xu, None, 1)
+            rt.call("wsl_softmax_bwd", rt.ptr(tu["s"]), rt.ptr(ds), rt.ptr(tu["dz"]), Nu, C_, HW, rt.stream())
+            lo[4:5].copy_(adv)
         elif kind == "semi_mt":
             zt = self._teacher_logits(xu, n0)             # usually already in flight on the side stream
             rt.call("wsl_softmax_mse_fwd_bwd", rt.ptr(z_u), rt.ptr(zt), rt.ptr(lo[4:]), rt.ptr(tu["dz"]), w, Nu, C_, HW, rt.ptr(lws), nl, rt.stream())
@@ -513,6 +548,59 @@ class TrainEngine:
             rt.call("wsl_ustm_consistency_fwd_bwd", rt.ptr(z_u), rt.ptr(zt), rt.ptr(tu["pm"]), float(thr), rt.ptr(lo[4:]), rt.ptr(tu["dz"]), w,
                     Nu, C_, HW, rt.ptr(lws), nl, rt.stream())
         self._finish_backward(xu, {"dz1": tu["dz"], "dz2": None}, kept=self._kept)
+
+    # ------------------------------------------------------------------ DAN: the adversary's own update
+    def _dan_target(self, n_l, n_u, both):
+        """both: DAN_target = [1] * N_l + [0] * N_u (train_deep_adversarial_network_2D.py:138-140); else its first N_u entries, the
+        generator update's target (line 152) -- all ones while N_u <= N_l, kept literal beyond"""
+        key = (n_l, n_u, both)
+        if key not in self._dan_targets:
+            full = [1] * n_l + [0] * n_u
+            self._dan_targets[key] = torch.tensor(full if both else full[:n_u], dtype=torch.int32, device=rt.device())
+        return self._dan_targets[key]
+
+    def discriminator_step(self, x_l, x_u, masks=None):
+        """The second half of a 'semi_dan' step (train_deep_adversarial_network_2D.py:162-176), after optimizer_step(): the student in
+        eval mode without gradient on both halves, softmax, the adversary in train mode on the concatenation, CE against
+        [1] * N_l + [0] * N_u, its parameter gradients only (conv0's data gradient is skipped), all-reduced as one bucket under data
+        parallelism, Adam.  masks = [m2 [N, 2 ndf], m3 [N, 4 ndf]] replays the two Dropout2d multipliers (0 or 2); None = drawn.
+        Leaves the student's parameters, gradient arena, BatchNorm running statistics and num_batches_tracked untouched."""
+        if self.loss_kind != "semi_dan":
+            raise _lib.WslError("discriminator_step belongs to the 'semi_dan' composition")
+        m, D = self.model, self.discriminator
+        x_l, x_u = rt.f32c(x_l, "image batch"), rt.f32c(x_u, "unlabeled image batch")
+        N, Nu, H, W, C_ = x_l.shape[0], x_u.shape[0], x_l.shape[2], x_l.shape[3], m.class_num
+        key = ("dan", N + Nu, H, W)
+        if key not in self._bufs:
+            self._bufs[key] = torch.empty((N + Nu, C_, H, W), dtype=torch.float32, device=x_l.device)
+        s = self._bufs[key]
+        m.eval()
+        try:
+            with torch.no_grad():
+                z_l = m._run_forward(x_l)[0]
+                rt.call("wsl_softmax_fwd", rt.ptr(z_l), rt.ptr(s), N, C_, H * W, rt.stream())
+                z_u = m._run_forward(x_u)[0]
+                rt.call("wsl_softmax_fwd", rt.ptr(z_u), rt.ptr(s[N:]), Nu, C_, H * W, rt.stream())
+        finally:
+            m.train()
+        xcat = torch.cat([x_l, x_u], 0)
+        D.train()
+        if masks is not None:
+            D.set_dropout_masks(masks)
+        try:
+            _, dl = D._run_forward(s, xcat, keep_for_backward=True, target=self._dan_target(N, Nu, True), gscale=1.0)
+        finally:
+            if masks is not None:
+                D.set_dropout_masks(None)
+        D._run_backward(s, xcat, None, 2)
+        if self.dp:
+            self._allreduce(D.flat_grads())
+            if self.comm is not None:
+                torch.cuda.current_stream().wait_stream(self.comm)
+        self.dan_it += 1
+        rt.call("wsl_adam_step", rt.ptr(D._param_arena), rt.ptr(D._grad_arena), rt.ptr(self.dan_m), rt.ptr(self.dan_v), D.n_param,
+                self.dan_lr, self.dan_betas[0], self.dan_betas[1], self.dan_eps, self.dan_it, 1.0 / self.world, rt.stream())
+        self.loss_out[5:6].copy_(dl)
 
     # ------------------------------------------------------------------ Scribble2Label: the running prediction average
     def ensemble_due(self):
@@ -654,6 +742,8 @@ class TrainEngine:
             d = {"loss": sup + self._semi_w * o[4], "ce": o[1], "dice": o[2], "sup": sup, "cons": o[4], "w": self._semi_w, "n_valid": o[3]}
             if self.loss_kind == "semi_uamt":
                 d["n_certain"], d["threshold"] = o[5], self._semi_thr
+            if self.loss_kind == "semi_dan":              # the adversary's own loss of the last discriminator_step
+                d["dan_loss"] = o[5]
             return d
         if self.loss_kind == "ce_dice":
             return {"loss": 0.5 * (o[1] + o[4]), "ce": o[1], "dice": o[4], "n_valid": o[3]}
