@@ -56,6 +56,7 @@ encoder's slice.  Losses stay on the device; `losses()` is the only host sync.
 """
 import ctypes as C
 import math
+import random
 
 import torch
 import torch.distributed as dist
@@ -63,6 +64,7 @@ import torch.distributed as dist
 from . import _lib
 from . import runtime as rt
 from .networks.net_factory import net_factory
+from .utils.ramps import sigmoid_rampup
 
 
 class TrainEngine:
@@ -93,12 +95,10 @@ class TrainEngine:
             raise _lib.WslError("'ours_proposed' needs the dual-branch unet_cct")
         if loss in self.REGULARISED and self.dual:
             raise _lib.WslError(f"'{loss}' is a single-branch (unet) composition")
-        if loss == "s2l" and self.dual:
-            raise _lib.WslError("'s2l' is a single-decoder composition (unet, pnet)")
-        if loss == "pce_interintra" and self.dual:
-            raise _lib.WslError("'pce_interintra' is a single-decoder composition (unet, pnet)")
-        if loss in self.SEMI and self.dual:
+        if loss in ("s2l", "pce_interintra") + self.SEMI and self.dual:
             raise _lib.WslError(f"'{loss}' is a single-decoder composition (unet, pnet)")
+        if loss in ("mean_teacher", "ustm") and self.dual:
+            raise _lib.WslError(f"'{loss}' is defined for the single-decoder unet")
         if teacher_update not in ("ema", "frozen"):
             raise ValueError(f"teacher_update {teacher_update!r} (one of 'ema', 'frozen')")
         self.loss_kind, self.w_pse, self.ignore = loss, w_pse, ignore_index
@@ -129,23 +129,13 @@ class TrainEngine:
         self.fused_heads = True                            # regulariser / mean-teacher loss heads through wsl_head_reg_fwd_bwd (False: the chain of calls)
         self.concurrent = True                             # teacher forward on a side stream; set False to serialise
         if loss in ("mean_teacher", "ustm"):
-            if self.dual:
-                raise _lib.WslError(f"'{loss}' is defined for the single-decoder unet")
-            self.teacher = net_factory(net_type, in_chns, class_num, conv_precision=self.model.conv_precision)
-            self.teacher.train()                          # the reference never puts the EMA model in eval()
-            with torch.no_grad():
-                self.teacher._param_arena.copy_(self.model._param_arena)
-                self.teacher._buf_arena.copy_(self.model._buf_arena)
+            self.teacher = self._make_teacher(net_type, in_chns, class_num)
             self.tv_weight, self.cons_max, self.ema_decay = 1e-2, 0.1, 0.99
         # semi-supervised trainers (train_mean_teacher_2D.py:60-66 --ema_decay / --consistency / --consistency_rampup, :73-75 the ramp)
         self.consistency, self.consistency_rampup, self.teacher_update = consistency, consistency_rampup, teacher_update
         self._semi_w, self._semi_thr, self._kept = 0.0, 0.0, None
         if loss in ("semi_mt", "semi_uamt"):
-            self.teacher = net_factory(net_type, in_chns, class_num, conv_precision=self.model.conv_precision)
-            self.teacher.train()                          # the reference never puts the EMA model in eval()
-            with torch.no_grad():
-                self.teacher._param_arena.copy_(self.model._param_arena)
-                self.teacher._buf_arena.copy_(self.model._buf_arena)
+            self.teacher = self._make_teacher(net_type, in_chns, class_num)
             self.ema_decay = ema_decay
         self.discriminator = None
         if loss == "semi_dan":
@@ -164,6 +154,15 @@ class TrainEngine:
             self.fused_heads = False
 
     # ------------------------------------------------------------------ helpers
+    def _make_teacher(self, net_type, in_chns, class_num):
+        """a second network that starts as a copy of the student: parameters and BatchNorm buffers"""
+        teacher = net_factory(net_type, in_chns, class_num, conv_precision=self.model.conv_precision)
+        teacher.train()                                   # the reference never puts the EMA model in eval()
+        with torch.no_grad():
+            teacher._param_arena.copy_(self.model._param_arena)
+            teacher._buf_arena.copy_(self.model._buf_arena)
+        return teacher
+
     def _tensors(self, N, H, W):
         key = (N, H, W)
         if key not in self._bufs:
@@ -172,13 +171,11 @@ class TrainEngine:
             t = {"dz1": mk(), "dz2": mk() if self.dual else None}
             if self.loss_kind == "pce_gatedcrf":
                 t["y"], t["msg"] = mk(), mk()
-            if self.loss_kind == "mean_teacher":
-                t["s"], t["ds"], t["dzx"] = mk(), mk(), mk()
             if self.loss_kind == "ustm":
                 t["zr"], t["dzx"], t["pm"] = mk(), mk(), mk()
-            if self.loss_kind in self.REGULARISED or self.loss_kind == "pce_interintra":
+            if self.loss_kind in self.REGULARISED + ("pce_interintra", "mean_teacher"):     # softmax(z), its gradient, a second dz
                 t["s"], t["ds"], t["dzx"] = mk(), mk(), mk()
-            self._bufs = {key: t}
+            self._bufs = {key: t}                         # deliberately ONE shape: a new (N, H, W) drops every buffer kept for the last
         return self._bufs[key]
 
     def _allreduce(self, flat):
@@ -221,9 +218,9 @@ class TrainEngine:
         rt.call("wsl_noisy_copy", rt.ptr(x), rt.ptr(noise), rt.ptr(out), x.numel(), reps, 0.1, 0.2, C.c_uint64(seed), rt.stream())
         return out
 
-    def _teacher_forward(self, x, noise):
+    def _teacher_forward(self, x, noise, reps=1):
         with torch.no_grad():
-            return self.teacher._run_forward(self._noisy(x, noise))[0]
+            return self.teacher._run_forward(self._noisy(x, noise, reps))[0]
 
     def _start_teacher(self, x, noise):
         """The teacher's forward is independent of the student's: on the GPU it runs on a side stream, forked here (before
@@ -246,44 +243,73 @@ class TrainEngine:
         zt, self._zt = self._zt, None
         return zt
 
+    # ------------------------------------------------------------------ the sequences of calls the compositions share
+    def _pce_head(self, z, label_u8, dz, w_ce, N, C_, HW, lws, nl):
+        """w_ce * pCE(z, label) of ONE decoder: loss_out[0..3], the gradient written to dz"""
+        rt.call("wsl_head_fwd_bwd", rt.ptr(z), None, rt.ptr(label_u8), self.ignore, 0.0, 0.0, w_ce, rt.ptr(self.loss_out), None,
+                rt.ptr(dz), None, N, C_, HW, rt.ptr(lws), nl, rt.stream())
+
+    def _head_reg(self, z, label_u8, reg_id, w, image, zt, w_cons, t, N, C_, H, W, lws, nl):
+        """one call: the head's first pass keeps softmax(z), the regulariser reg_id (WSL_REG_*; `image` where it reads one) turns it into
+        its weighted gradient, w_cons * softmax-MSE against the teacher logits zt joins where given, the head's second pass writes dz once"""
+        rt.call("wsl_head_reg_fwd_bwd", rt.ptr(z), rt.ptr(label_u8), self.ignore, 1.0, reg_id, w, rt.ptr(image), rt.ptr(zt), w_cons,
+                rt.ptr(self.loss_out), rt.ptr(t["dz1"]), rt.ptr(t["s"]), rt.ptr(t["ds"]), N, C_, H, W, rt.ptr(lws), nl, rt.stream())
+
+    def _softmax_term(self, z, t, dz, term, N, C_, HW, add=True):
+        """The gradient of a loss term on softmax(z): s = softmax(z) into t["s"]; term(s) enqueues the term and returns the tensor that holds
+        its gradient with respect to s; softmax backward -- into t["dzx"] and from there ADDED to dz, or (add=False) straight into dz."""
+        rt.call("wsl_softmax_fwd", rt.ptr(z), rt.ptr(t["s"]), N, C_, HW, rt.stream())
+        ds = term(t["s"])
+        out = t["dzx"] if add else dz
+        rt.call("wsl_softmax_bwd", rt.ptr(t["s"]), rt.ptr(ds), rt.ptr(out), N, C_, HW, rt.stream())
+        if add:
+            rt.call("wsl_axpy", rt.ptr(dz), rt.ptr(out), 1.0, N * C_ * HW, rt.stream())
+
+    def _dice(self, s, label_u8, w, t, N, C_, HW, lws, nl):
+        """DiceLoss(s, label) into loss_out[4], w times its gradient with respect to s into t["ds"] (returned)"""
+        if "dice" not in t:
+            t["dice"] = (torch.empty(3 * C_, dtype=torch.float32, device=s.device), torch.full((1,), w, dtype=torch.float32, device=s.device))
+        sums, gout = t["dice"]
+        rt.call("wsl_pdice_fwd", rt.ptr(s), rt.ptr(label_u8), 0, -1, rt.ptr(self.loss_out[4:]), rt.ptr(sums), N, C_, HW, rt.ptr(lws), nl, rt.stream())
+        rt.call("wsl_pdice_bwd", rt.ptr(s), rt.ptr(label_u8), 0, -1, rt.ptr(sums), rt.ptr(gout), rt.ptr(t["ds"]), N, C_, HW, rt.stream())
+        return t["ds"]
+
+    def _mc_teacher_mean(self, x, noises, pm, N, C_, HW):
+        """pm = the mean softmax of T = 8 stochastic teacher passes on x + noise, two per double batch (x.repeat(2, 1, 1, 1));
+        noises[1:]: the T//2 double-batch noises to replay (None: drawn)"""
+        T_ = 8
+        for i in range(T_ // 2):
+            z2 = self._teacher_forward(x, noises[1 + i] if noises is not None else None, reps=2)
+            for h in range(2):
+                rt.call("wsl_softmax_accum", rt.ptr(z2[h * N:]), rt.ptr(pm), 1.0 / T_, int(i == 0 and h == 0), N, C_, HW, rt.stream())
+
     def _regularised_losses(self, x, label_u8, z, t, lws, nl):
         """pCE + weight * R(softmax(z)) with R = tv_loss([1:]) | MumfordShah(image, .) | entropy_loss(., C), and the dense-label
         0.5 * (CE + DiceLoss) of the fully-supervised / random-walker scripts."""
         N, H, W = x.shape[0], x.shape[2], x.shape[3]
         HW, C_ = H * W, self.model.class_num
-        lo, w = self.loss_out, self.REG_WEIGHT[self.loss_kind]
-        if self.loss_kind in self.FUSED_REG and self.fused_heads:
-            # one call: the head's first pass keeps softmax(z), the regulariser turns it into its weighted gradient, the head's second
-            # pass writes dz once (wsl_head_reg_fwd_bwd; the chain below is kept for ce_dice and as the reference of the fused form)
-            rt.call("wsl_head_reg_fwd_bwd", rt.ptr(z), rt.ptr(label_u8), self.ignore, 1.0, self.FUSED_REG[self.loss_kind], w, rt.ptr(x),
-                    None, 0.0, rt.ptr(lo), rt.ptr(t["dz1"]), rt.ptr(t["s"]), rt.ptr(t["ds"]), N, C_, H, W, rt.ptr(lws), nl, rt.stream())
+        lo, kind, w = self.loss_out, self.loss_kind, self.REG_WEIGHT[self.loss_kind]
+        if kind in self.FUSED_REG and self.fused_heads:
+            # (wsl_head_reg_fwd_bwd; the chain below is kept for ce_dice and as the reference of the fused form)
+            self._head_reg(z, label_u8, self.FUSED_REG[kind], w, x, None, 0.0, t, N, C_, H, W, lws, nl)
             return
-        w_ce = 0.5 if self.loss_kind == "ce_dice" else 1.0
-        rt.call("wsl_head_fwd_bwd", rt.ptr(z), None, rt.ptr(label_u8), self.ignore, 0.0, 0.0, w_ce, rt.ptr(lo), None,
-                rt.ptr(t["dz1"]), None, N, C_, HW, rt.ptr(lws), nl, rt.stream())
-        rt.call("wsl_softmax_fwd", rt.ptr(z), rt.ptr(t["s"]), N, C_, HW, rt.stream())
-        if self.loss_kind == "pce_tv":
-            rt.call("wsl_tv_fwd_bwd", rt.ptr(t["s"]), 1, rt.ptr(lo[4:]), rt.ptr(t["ds"]), w, N, C_, H, W, rt.ptr(lws), nl, rt.stream())
-        elif self.loss_kind == "pce_ms":
-            rt.call("wsl_mumford_shah_fwd_bwd", rt.ptr(x), rt.ptr(t["s"]), rt.ptr(lo[4:]), rt.ptr(t["ds"]), w, N, C_, H, W,
-                    rt.ptr(lws), nl, rt.stream())
-        elif self.loss_kind == "ce_dice":
-            if "dice" not in t:
-                t["dice"] = (torch.empty(3 * C_, dtype=torch.float32, device=z.device),
-                             torch.full((1,), w, dtype=torch.float32, device=z.device))
-            sums, gout = t["dice"]
-            rt.call("wsl_pdice_fwd", rt.ptr(t["s"]), rt.ptr(label_u8), 0, -1, rt.ptr(lo[4:]), rt.ptr(sums), N, C_, HW,
-                    rt.ptr(lws), nl, rt.stream())
-            rt.call("wsl_pdice_bwd", rt.ptr(t["s"]), rt.ptr(label_u8), 0, -1, rt.ptr(sums), rt.ptr(gout), rt.ptr(t["ds"]),
-                    N, C_, HW, rt.stream())
-        else:
-            rt.call("wsl_entropy_fwd_bwd", rt.ptr(t["s"]), rt.ptr(lo[4:]), rt.ptr(t["ds"]), w, N, C_, HW, C_, rt.ptr(lws), nl, rt.stream())
-        rt.call("wsl_softmax_bwd", rt.ptr(t["s"]), rt.ptr(t["ds"]), rt.ptr(t["dzx"]), N, C_, HW, rt.stream())
-        rt.call("wsl_axpy", rt.ptr(t["dz1"]), rt.ptr(t["dzx"]), 1.0, N * C_ * HW, rt.stream())
+        self._pce_head(z, label_u8, t["dz1"], 0.5 if kind == "ce_dice" else 1.0, N, C_, HW, lws, nl)
+
+        def regulariser(s):
+            if kind == "pce_tv":
+                rt.call("wsl_tv_fwd_bwd", rt.ptr(s), 1, rt.ptr(lo[4:]), rt.ptr(t["ds"]), w, N, C_, H, W, rt.ptr(lws), nl, rt.stream())
+            elif kind == "pce_ms":
+                rt.call("wsl_mumford_shah_fwd_bwd", rt.ptr(x), rt.ptr(s), rt.ptr(lo[4:]), rt.ptr(t["ds"]), w, N, C_, H, W,
+                        rt.ptr(lws), nl, rt.stream())
+            elif kind == "ce_dice":
+                return self._dice(s, label_u8, w, t, N, C_, HW, lws, nl)
+            else:
+                rt.call("wsl_entropy_fwd_bwd", rt.ptr(s), rt.ptr(lo[4:]), rt.ptr(t["ds"]), w, N, C_, HW, C_, rt.ptr(lws), nl, rt.stream())
+            return t["ds"]
+        self._softmax_term(z, t, t["dz1"], regulariser, N, C_, HW)
 
     def var_weight(self, it=None):
         """w(t) of 'pce_interintra': get_current_consistency_weight(iter_num // 150) of the trainer (lines 68-70, 115)"""
-        from .utils.ramps import sigmoid_rampup
         return self.var_consistency * sigmoid_rampup((self.it if it is None else it) // 150, self.var_rampup)
 
     def _interintra_losses(self, x, label_u8, z, t, lws, nl):
@@ -292,72 +318,58 @@ class TrainEngine:
         HW, C_ = H * W, self.model.class_num
         if x.shape[1] != 1:
             raise NotImplementedError("the class-variance terms are built for a single-channel image")
-        lo, w = self.loss_out, self.var_weight()
-        self._var_w = w
+        w = self._var_w = self.var_weight()
         if self.fused_heads:      # out[4] = inter - intra, out[6] = inter, out[7] = intra
             self._var_slot = 4
-            rt.call("wsl_head_reg_fwd_bwd", rt.ptr(z), rt.ptr(label_u8), self.ignore, 1.0, 4, w, rt.ptr(x), None, 0.0, rt.ptr(lo),
-                    rt.ptr(t["dz1"]), rt.ptr(t["s"]), rt.ptr(t["ds"]), N, C_, H, W, rt.ptr(lws), nl, rt.stream())
+            self._head_reg(z, label_u8, 4, w, x, None, 0.0, t, N, C_, H, W, lws, nl)
             return
         self._var_slot = 5        # the stand-alone entry point writes {inter - intra, inter, intra} contiguously: slots 5, 6, 7
-        rt.call("wsl_head_fwd_bwd", rt.ptr(z), None, rt.ptr(label_u8), self.ignore, 0.0, 0.0, 1.0, rt.ptr(lo), None,
-                rt.ptr(t["dz1"]), None, N, C_, HW, rt.ptr(lws), nl, rt.stream())
-        rt.call("wsl_softmax_fwd", rt.ptr(z), rt.ptr(t["s"]), N, C_, HW, rt.stream())
-        rt.call("wsl_class_variance_fwd_bwd", rt.ptr(x), rt.ptr(t["s"]), rt.ptr(lo[5:]), rt.ptr(t["ds"]), w, -w, N, C_, H, W,
-                rt.ptr(lws), nl, rt.stream())
-        rt.call("wsl_softmax_bwd", rt.ptr(t["s"]), rt.ptr(t["ds"]), rt.ptr(t["dzx"]), N, C_, HW, rt.stream())
-        rt.call("wsl_axpy", rt.ptr(t["dz1"]), rt.ptr(t["dzx"]), 1.0, N * C_ * HW, rt.stream())
+        self._pce_head(z, label_u8, t["dz1"], 1.0, N, C_, HW, lws, nl)
+
+        def class_variance(s):
+            rt.call("wsl_class_variance_fwd_bwd", rt.ptr(x), rt.ptr(s), rt.ptr(self.loss_out[5:]), rt.ptr(t["ds"]), w, -w, N, C_, H, W,
+                    rt.ptr(lws), nl, rt.stream())
+            return t["ds"]
+        self._softmax_term(z, t, t["dz1"], class_variance, N, C_, HW)
 
     def _ustm_losses(self, x, label_u8, z, t, noise, lws, nl):
         """train_weakly_supervised_ustm_2D.py:119-157: pCE + w(t) * uncertainty-masked consistency.  `noise`: None (drawn
         like the script) or a list of T//2 + 1 tensors (teacher input noise, then the T//2 double-batch noises)."""
-        m, N, H, W = self.model, x.shape[0], x.shape[2], x.shape[3]
-        HW, C_, T_ = H * W, self.model.class_num, 8
+        N, H, W = x.shape[0], x.shape[2], x.shape[3]
+        HW, C_ = H * W, self.model.class_num
         if H != W:
             raise _lib.WslError("ustm rotates the batch by multiples of 90 degrees: square inputs only")
-        lo = self.loss_out
-        rt.call("wsl_head_fwd_bwd", rt.ptr(z), None, rt.ptr(label_u8), self.ignore, 0.0, 0.0, 1.0, rt.ptr(lo), None,
-                rt.ptr(t["dz1"]), None, N, C_, HW, rt.ptr(lws), nl, rt.stream())
-        import random as _random
-        k = _random.randrange(0, 4)                           # ustm_2D.py:121 (the script's only python-RNG draw per step)
+        self._pce_head(z, label_u8, t["dz1"], 1.0, N, C_, HW, lws, nl)
+        k = random.randrange(0, 4)                            # ustm_2D.py:121 (the script's only python-RNG draw per step)
         xr = torch.empty_like(x)
         rt.call("wsl_rot90", rt.ptr(x), rt.ptr(xr), N * x.shape[1], H, W, k, rt.stream())
-
-        with torch.no_grad():
-            zt = self.teacher._run_forward(self._noisy(xr, noise[0] if noise is not None else None))[0]
-            for i in range(T_ // 2):                          # T stochastic passes, two per double batch (xr.repeat(2, 1, 1, 1))
-                z2 = self.teacher._run_forward(self._noisy(xr, noise[1 + i] if noise is not None else None, reps=2))[0]
-                for h in range(2):
-                    rt.call("wsl_softmax_accum", rt.ptr(z2[h * N:]), rt.ptr(t["pm"]), 1.0 / T_, int(i == 0 and h == 0), N, C_,
-                            HW, rt.stream())
-        from .utils.ramps import sigmoid_rampup
+        zt = self._teacher_forward(xr, noise[0] if noise is not None else None)
+        self._mc_teacher_mean(xr, noise, t["pm"], N, C_, HW)
         self._cons_w = 1.0 * sigmoid_rampup(self.it // 1000, 60)      # ustm_2D.py:56-58,146: get_current_consistency_weight(iter // 1000)
-        thr = (0.75 + 0.25 * sigmoid_rampup(self.it, self.max_it)) * math.log(2.0)
+        thr = self.uncertainty_threshold()
         rt.call("wsl_rot90", rt.ptr(z), rt.ptr(t["zr"]), N * C_, H, W, k, rt.stream())
-        rt.call("wsl_ustm_consistency_fwd_bwd", rt.ptr(t["zr"]), rt.ptr(zt), rt.ptr(t["pm"]), float(thr), rt.ptr(lo[4:]),
+        rt.call("wsl_ustm_consistency_fwd_bwd", rt.ptr(t["zr"]), rt.ptr(zt), rt.ptr(t["pm"]), float(thr), rt.ptr(self.loss_out[4:]),
                 rt.ptr(t["dzx"]), self._cons_w, N, C_, HW, rt.ptr(lws), nl, rt.stream())
         rt.call("wsl_rot90", rt.ptr(t["dzx"]), rt.ptr(t["zr"]), N * C_, H, W, 4 - k, rt.stream())    # gradient back through rot90
         rt.call("wsl_axpy", rt.ptr(t["dz1"]), rt.ptr(t["zr"]), 1.0, N * C_ * HW, rt.stream())
 
     def _mean_teacher_losses(self, x, label_u8, z, t, noise, lws, nl):
         """dz of pCE + tv + consistency for the student logits z; teacher logits from x + noise (no gradient)."""
-        m, N, H, W = self.model, x.shape[0], x.shape[2], x.shape[3]
+        N, H, W = x.shape[0], x.shape[2], x.shape[3]
         HW, C_ = H * W, self.model.class_num
         zt = self._teacher_logits(x, noise)                # usually already in flight on the side stream
         lo = self.loss_out
-        from .utils.ramps import sigmoid_rampup
         self._cons_w = self.cons_max * sigmoid_rampup(self.it // 300, 200.0)
         if self.fused_heads:      # pCE + tv_weight * TV(softmax[1:]) + w(t) * softmax-MSE(student, teacher): one call, dz written once
-            rt.call("wsl_head_reg_fwd_bwd", rt.ptr(z), rt.ptr(label_u8), self.ignore, 1.0, 1, self.tv_weight, None, rt.ptr(zt),
-                    self._cons_w, rt.ptr(lo), rt.ptr(t["dz1"]), rt.ptr(t["s"]), rt.ptr(t["ds"]), N, C_, H, W, rt.ptr(lws), nl, rt.stream())
+            self._head_reg(z, label_u8, 1, self.tv_weight, None, zt, self._cons_w, t, N, C_, H, W, lws, nl)
             return
-        rt.call("wsl_head_fwd_bwd", rt.ptr(z), None, rt.ptr(label_u8), self.ignore, 0.0, 0.0, 1.0, rt.ptr(lo), None,
-                rt.ptr(t["dz1"]), None, N, C_, HW, rt.ptr(lws), nl, rt.stream())
-        rt.call("wsl_softmax_fwd", rt.ptr(z), rt.ptr(t["s"]), N, C_, HW, rt.stream())
-        rt.call("wsl_tv_fwd_bwd", rt.ptr(t["s"]), 1, rt.ptr(lo[4:]), rt.ptr(t["ds"]), self.tv_weight, N, C_, H, W, rt.ptr(lws),
-                nl, rt.stream())
-        rt.call("wsl_softmax_bwd", rt.ptr(t["s"]), rt.ptr(t["ds"]), rt.ptr(t["dzx"]), N, C_, HW, rt.stream())
-        rt.call("wsl_axpy", rt.ptr(t["dz1"]), rt.ptr(t["dzx"]), 1.0, N * C_ * HW, rt.stream())
+        self._pce_head(z, label_u8, t["dz1"], 1.0, N, C_, HW, lws, nl)
+
+        def tv(s):
+            rt.call("wsl_tv_fwd_bwd", rt.ptr(s), 1, rt.ptr(lo[4:]), rt.ptr(t["ds"]), self.tv_weight, N, C_, H, W, rt.ptr(lws), nl,
+                    rt.stream())
+            return t["ds"]
+        self._softmax_term(z, t, t["dz1"], tv, N, C_, HW)
         rt.call("wsl_softmax_mse_fwd_bwd", rt.ptr(z), rt.ptr(zt), rt.ptr(lo[5:]), rt.ptr(t["dzx"]), self._cons_w, N, C_, HW,
                 rt.ptr(lws), nl, rt.stream())
         rt.call("wsl_axpy", rt.ptr(t["dz1"]), rt.ptr(t["dzx"]), 1.0, N * C_ * HW, rt.stream())
@@ -422,13 +434,11 @@ class TrainEngine:
     def consistency_weight(self, it=None):
         """w(t) of the 'semi_*' compositions: get_current_consistency_weight(iter_num // 300) (train_mean_teacher_2D.py:73-75, 164-165)
         -- iter_num // 150 for 'semi_dan' (train_deep_adversarial_network_2D.py:153); consistency_rampup = 0: the constant weight"""
-        from .utils.ramps import sigmoid_rampup
         div = 150 if self.loss_kind == "semi_dan" else 300
         return self.consistency * sigmoid_rampup((self.it if it is None else it) // div, self.consistency_rampup)
 
     def uncertainty_threshold(self, it=None):
         """(0.75 + 0.25 * sigmoid_rampup(iter_num, max_iterations)) * ln 2 (train_uncertainty_aware_mean_teacher_2D.py:184-185)"""
-        from .utils.ramps import sigmoid_rampup
         return (0.75 + 0.25 * sigmoid_rampup(self.it if it is None else it, self.max_it)) * math.log(2.0)
 
     def _set_masks(self, mk):
@@ -446,16 +456,8 @@ class TrainEngine:
             return
         # the chain `ce_dice` runs: head (0.5 * CE), softmax, DiceLoss forward / backward, softmax backward, axpy; the Dice value lands in
         # loss_out[4] and moves to slot 2 (the head's unused `pse`), so both routes leave the same layout
-        if "dice" not in t:
-            t["dice"] = (torch.empty(3 * C_, dtype=torch.float32, device=z.device), torch.full((1,), 0.5, dtype=torch.float32, device=z.device))
-        sums, gout = t["dice"]
-        rt.call("wsl_head_fwd_bwd", rt.ptr(z), None, rt.ptr(label_u8), self.ignore, 0.0, 0.0, 0.5, rt.ptr(lo), None, rt.ptr(dz), None,
-                N, C_, HW, rt.ptr(lws), nl, rt.stream())
-        rt.call("wsl_softmax_fwd", rt.ptr(z), rt.ptr(t["s"]), N, C_, HW, rt.stream())
-        rt.call("wsl_pdice_fwd", rt.ptr(t["s"]), rt.ptr(label_u8), 0, -1, rt.ptr(lo[4:]), rt.ptr(sums), N, C_, HW, rt.ptr(lws), nl, rt.stream())
-        rt.call("wsl_pdice_bwd", rt.ptr(t["s"]), rt.ptr(label_u8), 0, -1, rt.ptr(sums), rt.ptr(gout), rt.ptr(t["ds"]), N, C_, HW, rt.stream())
-        rt.call("wsl_softmax_bwd", rt.ptr(t["s"]), rt.ptr(t["ds"]), rt.ptr(t["dzx"]), N, C_, HW, rt.stream())
-        rt.call("wsl_axpy", rt.ptr(dz), rt.ptr(t["dzx"]), 1.0, N * C_ * HW, rt.stream())
+        self._pce_head(z, label_u8, dz, 0.5, N, C_, HW, lws, nl)
+        self._softmax_term(z, t, dz, lambda s: self._dice(s, label_u8, 0.5, t, N, C_, HW, lws, nl), N, C_, HW)
         lo[2:3].copy_(lo[4:5])      # (slot 0 holds the head's plain CE on this route: losses() forms sup from ce and dice on both)
 
     def _semi_tensors(self, N, H, W, which):
@@ -520,30 +522,28 @@ class TrainEngine:
             if self.fused_heads:
                 rt.call("wsl_entropy_logits_fwd_bwd", rt.ptr(z_u), rt.ptr(lo[4:]), rt.ptr(tu["dz"]), w, Nu, C_, HW, 4, rt.ptr(lws), nl, rt.stream())
             else:
-                rt.call("wsl_softmax_fwd", rt.ptr(z_u), rt.ptr(tu["s"]), Nu, C_, HW, rt.stream())
-                rt.call("wsl_entropy_fwd_bwd", rt.ptr(tu["s"]), rt.ptr(lo[4:]), rt.ptr(tu["ds"]), w, Nu, C_, HW, 4, rt.ptr(lws), nl, rt.stream())
-                rt.call("wsl_softmax_bwd", rt.ptr(tu["s"]), rt.ptr(tu["ds"]), rt.ptr(tu["dz"]), Nu, C_, HW, rt.stream())
+                def entropy(s):
+                    rt.call("wsl_entropy_fwd_bwd", rt.ptr(s), rt.ptr(lo[4:]), rt.ptr(tu["ds"]), w, Nu, C_, HW, 4, rt.ptr(lws), nl, rt.stream())
+                    return tu["ds"]
+                self._softmax_term(z_u, tu, tu["dz"], entropy, Nu, C_, HW, add=False)
         elif kind == "semi_dan":
             # w * CE(DAN(softmax(z_u), x_u), t_u): the adversary in eval mode, its loss differentiated into softmax(z_u) only (no weight
             # gradient: the reference discards them), the weight w folded into the head's gradient scale
-            D = self.discriminator
+            D, adv = self.discriminator, None
             D.eval()
-            rt.call("wsl_softmax_fwd", rt.ptr(z_u), rt.ptr(tu["s"]), Nu, C_, HW, rt.stream())
-            _, adv = D._run_forward(tu["s"], xu, keep_for_backward=True, target=self._dan_target(N, Nu, False), gscale=float(w))
-            ds = D._run_backward(tu["s"], xu, None, 1)
-            rt.call("wsl_softmax_bwd", rt.ptr(tu["s"]), rt.ptr(ds), rt.ptr(tu["dz"]), Nu, C_, HW, rt.stream())
+
+            def adversary(s):                             # -> the data gradient its backward returns
+                nonlocal adv
+                _, adv = D._run_forward(s, xu, keep_for_backward=True, target=self._dan_target(N, Nu, False), gscale=float(w))
+                return D._run_backward(s, xu, None, 1)
+            self._softmax_term(z_u, tu, tu["dz"], adversary, Nu, C_, HW, add=False)
             lo[4:5].copy_(adv)
         elif kind == "semi_mt":
             zt = self._teacher_logits(xu, n0)             # usually already in flight on the side stream
             rt.call("wsl_softmax_mse_fwd_bwd", rt.ptr(z_u), rt.ptr(zt), rt.ptr(lo[4:]), rt.ptr(tu["dz"]), w, Nu, C_, HW, rt.ptr(lws), nl, rt.stream())
         else:
-            T_ = 8
             zt = self._teacher_logits(xu, n0)             # joins the side stream: the passes below reuse the teacher's workspace
-            with torch.no_grad():
-                for i in range(T_ // 2):                  # T stochastic passes, two per double batch (x_u.repeat(2, 1, 1, 1))
-                    z2 = self.teacher._run_forward(self._noisy(xu, noise[1 + i] if noise is not None else None, reps=2))[0]
-                    for h in range(2):
-                        rt.call("wsl_softmax_accum", rt.ptr(z2[h * Nu:]), rt.ptr(tu["pm"]), 1.0 / T_, int(i == 0 and h == 0), Nu, C_, HW, rt.stream())
+            self._mc_teacher_mean(xu, noise, tu["pm"], Nu, C_, HW)
             thr = self._semi_thr = self.uncertainty_threshold()
             rt.call("wsl_ustm_consistency_fwd_bwd", rt.ptr(z_u), rt.ptr(zt), rt.ptr(tu["pm"]), float(thr), rt.ptr(lo[4:]), rt.ptr(tu["dz"]), w,
                     Nu, C_, HW, rt.ptr(lws), nl, rt.stream())
@@ -656,8 +656,7 @@ class TrainEngine:
                         z = torch.empty((n, C_, Hn, Wn), dtype=torch.float32, device=dev)
                         for j, idx in enumerate(idxs):
                             if masks is not None:
-                                mk = masks[idx]
-                                m.set_dropout_masks(*mk) if isinstance(mk, tuple) else m.set_dropout_masks(mk)
+                                self._set_masks(masks[idx])
                             z[j:j + 1].copy_(m._run_forward(x[j:j + 1])[0])
                     rt.call("wsl_s2l_ensemble_update", rt.ptr(z), slots, n, C_, Hn, Wn, float(self.s2l_alpha), rt.stream())
         finally:
