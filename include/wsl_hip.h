@@ -188,6 +188,30 @@ int wsl_bnact_bwd_finish_d_amax(const float* dz, int64_t dz_bs, const float* y, 
                                 const float* gamma, const float* beta, float* dy, float* dgamma, float* dbeta, int N, int C, int H,
                                 int W, const float* part, int nblk, int channel_major, void* ws, size_t ws_bytes, uint32_t* dy_amax,
                                 void* stream);
+/* The data gradient g of a layer AND the whole backward of the BatchNorm + LeakyReLU (no dropout) that produced its input, in one call:
+ * dy_in -> dy_out [N,Co,H,W] dense, dgamma, dbeta.  Where the narrow-K kernel takes the launch (ks 3, 4 -> 16 channels, packed weights:
+ * wmode 3, H % 8 == 0, W % 64 == 0, float4-aligned tensors) and dy_amax is NULL, g is never written: a statistics pass leaves the
+ * partials in bn_part, they are finalized into coef_ws, and an apply pass recomputes g on the matrix cores and stores dy_out with
+ * wsl_bnact_bwd_finish's arithmetic (*route = 2; the same bits as route 1; `g` is untouched).  Everywhere else: wsl_conv2d_dgrad_bn_d
+ * into g followed by wsl_bnact_bwd_finish_d_amax / _finish_amax (*route = 1) or wsl_bnact_bwd_amax (*route = 0), exactly those
+ * launches.  bn_part: max(partials of wsl_conv2d_dgrad_bn, wsl_bnact_bwd_ws_bytes()) bytes; coef_ws: wsl_bnact_bwd_finish_ws_bytes(). */
+int wsl_conv2d_dgrad_bn_dy(const WslSrc* dy_in, const float* w, float* g, int N, int H, int W, int Co, int ks, int wmode,
+                           const float* bn_y, const float* bn_st, const float* gamma, const float* beta, float* bn_part,
+                           size_t bn_part_bytes, float* dy_out, float* dgamma, float* dbeta, void* coef_ws, size_t coef_ws_bytes,
+                           uint32_t* dy_amax, int* route, void* stream);
+/* A layer WITHOUT a data gradient (the first convolution) has one reader of its dy, the weight gradient: its apply pass need not write
+ * dy at all.  wsl_bnact_bwd_coef = the finalize half of wsl_bnact_bwd_finish alone (dgamma, dbeta, coef[C][2] = (S1/n, S2/n) from the
+ * producer's partials); wsl_conv2d_wgrad_bnd_partial = wsl_conv2d_wgrad_partial whose dy is VIRTUAL: the kernel's loader reads dz and y
+ * and forms dy = gamma*invstd*(dz - S1/n - xhat*S2/n) with the arithmetic of wsl_bnact_bwd_finish_d_amax's pass (the same bits), so dw
+ * and db equal the two-launch route's exactly.  Available where wsl_conv2d_wgrad_bnd_ok() != 0: ks 3, one raw 1-channel source, Co 16,
+ * H % 8 == 0, W % 64 == 0, float4-aligned tensors; everything else is an error there (the caller takes the two-launch route). */
+int wsl_bnact_bwd_coef(const float* part, int nblk, int channel_major, int N, int C, int H, int W, float* dgamma, float* dbeta,
+                       float* coef, void* stream);
+int wsl_conv2d_wgrad_bnd_ok(const WslSrc* a, const WslSrc* b, const float* dz, int64_t dz_bs, const float* y, int64_t y_bs, int H,
+                            int W, int Co, int ks);
+int wsl_conv2d_wgrad_bnd_partial(const WslSrc* a, const float* dz, int64_t dz_bs, const float* y, int64_t y_bs, const float* mean,
+                                 const float* invstd, const float* gamma, const float* coef, float* dw, float* db, int N, int H, int W,
+                                 int Co, int ks, void* ws, size_t ws_bytes, WslWgradPending* pending, void* stream);
 
 /* ------------------------------------------------------------------------------------------------ split-precision conv path
  * (opt-in; ref semantics unchanged: networks/unet.py:13-29.)  The 3x3 convolutions on the f16 matrix cores

@@ -112,6 +112,12 @@ _PROTOS = {
     "wsl_conv2d_dgrad_bn_d": (i32, [PS, c_fp, c_fp, i64, i32, i32, i32, i32, i32, i32, c_fp, c_fp, c_fp, f32, c_fp, C.POINTER(C.c_int), c_fp]),
     "wsl_bnact_bwd_finish_d_amax": (i32, [c_fp, i64, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, i32, i32, i32, i32,
                                           c_fp, i32, i32, c_fp, sz, c_fp, c_fp]),
+    "wsl_conv2d_dgrad_bn_dy": (i32, [PS, c_fp, c_fp, i32, i32, i32, i32, i32, i32, c_fp, c_fp, c_fp, c_fp, c_fp, sz, c_fp, c_fp, c_fp,
+                                     c_fp, sz, c_fp, C.POINTER(C.c_int), c_fp]),
+    "wsl_bnact_bwd_coef": (i32, [c_fp, i32, i32, i32, i32, i32, i32, c_fp, c_fp, c_fp, c_fp]),
+    "wsl_conv2d_wgrad_bnd_ok": (i32, [PS, PS, c_fp, i64, c_fp, i64, i32, i32, i32, i32]),
+    "wsl_conv2d_wgrad_bnd_partial": (i32, [PS, c_fp, i64, c_fp, i64, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, i32, i32, i32, i32, i32,
+                                           c_fp, sz, C.POINTER(WslWgradPending), c_fp]),
     "wsl_feat_grad_combine_blocks": (i32, [i32, i32, i32]),
     "wsl_feat_grad_combine_bn": (i32, [PS, c_fp, i64, c_fp, i64, c_fp, c_fp, c_fp, i32, i32, i32, c_fp, c_fp, c_fp, c_fp]),
     "wsl_bnact_bwd_finish": (i32, [c_fp, i64, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, f32, c_fp, c_fp, c_fp, i32, i32, i32, i32,

@@ -326,7 +326,7 @@ __device__ __forceinline__ void bn_dz4(const BnBwdP& p, int n, int c, int i, flo
   float g4[4] = {gv.x, gv.y, gv.z, gv.w};
   if (p.g_is_d) {   // (kernel argument: uniform)
 #pragma unroll
-    for (int k = 0; k < 4; ++k) xh[k] = (y4[k] - mean) * invstd, d[k] = g4[k];
+    for (int k = 0; k < 4; ++k) xh[k] = bn_bwd_xhat(y4[k], mean, invstd), d[k] = g4[k];
     return;
   }
   if (p.emask) {
@@ -337,7 +337,7 @@ __device__ __forceinline__ void bn_dz4(const BnBwdP& p, int n, int c, int i, flo
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const float z = fmaf(y4[k], sc, sh);
-    xh[k] = (y4[k] - mean) * invstd;
+    xh[k] = bn_bwd_xhat(y4[k], mean, invstd);
     d[k] = z > 0.f ? g4[k] : WSL_LEAKY_SLOPE * g4[k];
   }
 }
@@ -416,8 +416,8 @@ __global__ __launch_bounds__(256) void bnact_bwd_apply4_kernel(BnBwdP p, const f
   for (int i = base + 4 * threadIdx.x; i < base + kChunk && i < p.HW; i += 4 * kThreads) {
     float d[4], xh[4];
     bn_dz4(p, n, c, i, sc, sh, mean, invstd, d, xh);
-    const float4 v = make_float4(sc * (d[0] - c1 - xh[0] * c2), sc * (d[1] - c1 - xh[1] * c2), sc * (d[2] - c1 - xh[2] * c2),
-                                 sc * (d[3] - c1 - xh[3] * c2));
+    const float4 v = make_float4(bn_bwd_dy(d[0], xh[0], sc, c1, c2), bn_bwd_dy(d[1], xh[1], sc, c1, c2), bn_bwd_dy(d[2], xh[2], sc, c1, c2),
+                                 bn_bwd_dy(d[3], xh[3], sc, c1, c2));
     *reinterpret_cast<float4*>(dy + ((int64_t)n * p.C + c) * p.HW + i) = v;
     if (pmax) m = fmaxf(fmaxf(m, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
   }
@@ -839,6 +839,22 @@ extern "C" size_t wsl_bnact_bwd_finish_ws_bytes(int N, int C, int H, int W, int 
   return sizeof(float) * (2 * (size_t)C + (with_amax ? (size_t)N * cdiv(H * W, kChunk) * C : 0));
 }
 
+// stage 2a of the BatchNorm backward from a producer's partial sums: dgamma, dbeta and the apply pass' coefficients coef[C][2]
+static void bnact_bwd_finalize_launch(const float* part, int nblk, int C, int channel_major, double count, float* dgamma, float* dbeta,
+                                      float* coef, void* stream) {
+  WSL_LAUNCH(bnact_bwd_finalize_kernel, dim3(C), dim3(finalize_threads(nblk)), 0, stream, part, nblk, C,
+             channel_major ? (int64_t)1 : (int64_t)C, channel_major ? (int64_t)nblk : (int64_t)1, count, dgamma, dbeta, coef);
+}
+
+extern "C" int wsl_bnact_bwd_coef(const float* part, int nblk, int channel_major, int N, int C, int H, int W, float* dgamma,
+                                  float* dbeta, float* coef, void* stream) {
+  WSL_REQUIRE(part && coef, "bnact_bwd_coef: null argument");
+  WSL_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0 && nblk > 0, "bnact_bwd_coef: bad shape");
+  ProfScope ps(PF_BN_BWD, 0.0, 4.0 * (2.0 * nblk * C + 4.0 * C), stream);
+  bnact_bwd_finalize_launch(part, nblk, C, channel_major, (double)N * H * W, dgamma, dbeta, coef, stream);
+  return check_launch("bnact_bwd_coef");
+}
+
 static int bnact_bwd_finish_impl(const float* g, int64_t g_bs, const float* y, const float* mean, const float* invstd,
                                  const float* gamma, const float* beta, const uint8_t* emask, float emask_scale, float* dy,
                                  float* dgamma, float* dbeta, int N, int C, int H, int W, const float* part, int nblk,
@@ -857,9 +873,7 @@ static int bnact_bwd_finish_impl(const float* g, int64_t g_bs, const float* y, c
   auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   const bool vec = (H * W) % 4 == 0 && (g_bs % 4) == 0 && al16(g) && al16(y) && al16(dy) &&
                    (!emask || (reinterpret_cast<uintptr_t>(emask) & 3) == 0);
-  WSL_LAUNCH(bnact_bwd_finalize_kernel, dim3(C), dim3(finalize_threads(nblk)), 0, stream, part, nblk, C,
-             channel_major ? (int64_t)1 : (int64_t)C, channel_major ? (int64_t)nblk : (int64_t)1, (double)N * H * W, dgamma, dbeta,
-             coef);
+  bnact_bwd_finalize_launch(part, nblk, C, channel_major, (double)N * H * W, dgamma, dbeta, coef, stream);
   uint32_t* pmax = dy_amax ? reinterpret_cast<uint32_t*>(coef + 2 * (size_t)C) : nullptr;
   if (vec) WSL_LAUNCH(bnact_bwd_apply4_kernel, grid, dim3(kThreads), 0, stream, p, coef, dy, pmax);
   else WSL_LAUNCH(bnact_bwd_apply_kernel, grid, dim3(kThreads), 0, stream, p, coef, dy, pmax);

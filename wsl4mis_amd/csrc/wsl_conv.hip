@@ -568,6 +568,9 @@ int conv2_fwd(const WslSrc& a, const WslSrc* b, const float* wp, const float* bi
 int wgrad_small_kind(const WslSrc& a, const WslSrc* b, int H, int W, int Co, int ks);   // wsl_conv4.hip
 int wgrad_small_launch(int kind, const WslSrc& a, const float* dy, int64_t dy_bs, float* part_dw, float* part_db, int N,
                        int H, int W, int nsplit, void* stream);
+int wgrad_small_launch_bnd(const WslSrc& a, const float* d, int64_t d_bs, const float* y, int64_t y_bs, const float* mean,
+                           const float* invstd, const float* gamma, const float* coef, float* part_dw, float* part_db, int N, int H,
+                           int W, int nsplit, void* stream);
 bool conv_cls_eligible(const WslSrc& a, const WslSrc* b, const float* y, int64_t y_bs, int H, int W, int Co, int ks,
                        const float* stat_part);                                              // wsl_conv4.hip
 bool conv_nk16_eligible(const WslSrc& a, const WslSrc* b, const float* y, int64_t y_bs, int H, int W, int Co, int ks, int th, int tw);
@@ -575,6 +578,9 @@ int conv_nk16_launch(const WslSrc& a, const float* wp, const float* bias, float*
                      float* stat_part, float* stat_cnt, int slots, const BnBwdEpi* bn, int* bn_done, void* stream);
 int conv_cls_launch(const WslSrc& a, const float* wp, const float* bias, float* y, int64_t y_bs, int N, int H, int W,
                     void* stream);
+int conv_nk16_stats_launch(const WslSrc& a, const float* wp, int N, int H, int W, const BnBwdEpi& bn, void* stream);   // wsl_conv4.hip
+int conv_nk16_apply_launch(const WslSrc& a, const float* wp, int N, int H, int W, const BnBwdEpi& bn, const float* gamma,
+                           const float* beta, const float* coef, float* dy, void* stream);
 int wino_pack(const float* w, float* u, int Co, int Ci, int dgrad, void* stream);   // wsl_conv5.hip
 int wino_fwd(const WslSrc& a, const WslSrc* b, const float* u, const float* bias, float* y, int64_t y_bs, int N, int H,
              int W, int Co, int is_dgrad, float* stat_part, float* stat_cnt, int slots, void* stream,
@@ -636,6 +642,11 @@ extern "C" int wsl_conv2d_stat_blocks(int N, int H, int W, int Ci, int Co, int k
   return N * cdiv(H, f.th) * cdiv(W, f.tw);
 }
 
+static bool conv_nk16_on() {
+  static const bool on = (WSL_TUNE("WSL_CONV_NK16", 1) != 0);
+  return on;
+}
+
 static int conv2d_fwd_impl(const WslSrc* a, const WslSrc* b, const float* w, const float* bias, float* y, int64_t y_bs, int N,
                            int H, int W, int Co, int ks, int wmode, float* stat_part, float* stat_cnt, void* stream,
                            const BnBwdEpi* bn, int* bn_done) {
@@ -669,8 +680,7 @@ static int conv2d_fwd_impl(const WslSrc* a, const WslSrc* b, const float* w, con
       WSL_REQUIRE(f.wino, "conv2d_fwd: wmode %d needs wsl_conv2d_wino_ok() != 0 for this layer", wmode);
       return wino_fwd(p.in.a, &p.in.b, w, bias, y, y_bs, N, H, W, Co, wmode == 5, stat_part, stat_cnt, p.slots, stream, bn, bn_done);
     }
-    static const bool nk_on = (WSL_TUNE("WSL_CONV_NK16", 1) != 0);
-    if (nk_on && conv_nk16_eligible(p.in.a, &p.in.b, y, y_bs, H, W, Co, ks, f.th, f.tw))
+    if (conv_nk16_on() && conv_nk16_eligible(p.in.a, &p.in.b, y, y_bs, H, W, Co, ks, f.th, f.tw))
       return conv_nk16_launch(p.in.a, w, bias, y, y_bs, N, H, W, wmode == 3, stat_part, stat_cnt, p.slots, bn, bn_done,
                               stream);   // first conv forward / classifier data gradient (wsl_conv4.hip)
     static const bool cls_on = (WSL_TUNE("WSL_CONV_CLS", 1) != 0);
@@ -715,6 +725,53 @@ extern "C" int wsl_conv2d_dgrad_bn_d(const WslSrc* dy, const float* w, float* g,
   return dgrad_bn_impl(dy, w, g, g_bs, N, H, W, Co, ks, wmode, bn_y, bn_st, bn_emask, bn_emask_scale, bn_part, fused, true, stream);
 }
 
+// Data gradient of a layer + the whole BatchNorm + LeakyReLU backward of the layer that consumes it (no dropout), dy_in -> dy_out.
+//   *route = 2: the narrow-K kernel in two passes with the finalize between them -- g is recomputed, never written (`g` stays untouched)
+//   *route = 1 / 0: wsl_conv2d_dgrad_bn_d into `g`, then wsl_bnact_bwd_finish*_amax (1: statistics from the epilogue) or
+//                   wsl_bnact_bwd_amax (0) -- the launches a caller of those entry points issues, in that order
+// Route 2 is taken where the launch is the narrow-K data gradient (4 -> 16 channels, packed weights, 8 x 64 tiles), its epilogue would
+// carry the statistics, and nobody wants max |dy| (the split path's apply pass leaves it; the recomputing pass does not).
+extern "C" int wsl_conv2d_dgrad_bn_dy(const WslSrc* dy, const float* w, float* g, int N, int H, int W, int Co, int ks, int wmode,
+                                      const float* bn_y, const float* bn_st, const float* gamma, const float* beta, float* bn_part,
+                                      size_t bn_part_bytes, float* dy_out, float* dgamma, float* dbeta, void* coef_ws,
+                                      size_t coef_ws_bytes, uint32_t* dy_amax, int* route, void* stream) {
+  WSL_REQUIRE(dy && w && g && bn_y && bn_st && gamma && beta && bn_part && dy_out && coef_ws && route, "conv2d_dgrad_bn_dy: null argument");
+  WSL_REQUIRE(N > 0 && H > 0 && W > 0 && Co > 0, "conv2d_dgrad_bn_dy: bad shape");
+  *route = 0;
+  const int64_t g_bs = (int64_t)Co * H * W;
+  const float *mean = bn_st, *invstd = bn_st + Co;
+  const WslSrc none{};
+  const bool two_pass = !dy_amax && wmode == 3 && dy->C == 4 && conv_nk16_on() && conv2_eligible(*dy, &none, dy_out, g_bs, W, dy->C) &&
+                        conv_nk16_eligible(*dy, &none, dy_out, g_bs, H, W, Co, ks, fwd_plan(N, H, W, Co, dy->C, ks).th,
+                                           fwd_plan(N, H, W, Co, dy->C, ks).tw) &&
+                        !(reinterpret_cast<uintptr_t>(bn_y) & 15);   // (W % 64 == 0, dense g: the statistics would be fused)
+  if (two_pass) {
+    if (int rc = check_src(dy, H * W, "conv2d_dgrad_bn_dy(dy)")) return rc;
+    const int nblk = wsl_conv2d_stat_blocks(N, H, W, dy->C, Co, ks);
+    WSL_REQUIRE(coef_ws_bytes >= sizeof(float) * 2 * (size_t)Co && bn_part_bytes >= sizeof(float) * 2 * (size_t)Co * nblk,
+                "conv2d_dgrad_bn_dy: workspace too small");
+    BnBwdEpi e;
+    e.y = bn_y, e.st = bn_st, e.part = bn_part;
+    float* coef = static_cast<float*>(coef_ws);
+    if (int rc = conv_nk16_stats_launch(*dy, w, N, H, W, e, stream)) return rc;
+    if (int rc = wsl_bnact_bwd_coef(bn_part, nblk, 1, N, Co, H, W, dgamma, dbeta, coef, stream)) return rc;
+    *route = 2;
+    return conv_nk16_apply_launch(*dy, w, N, H, W, e, gamma, beta, coef, dy_out, stream);
+  }
+  int fused = 0;
+  if (int rc = dgrad_bn_impl(dy, w, g, g_bs, N, H, W, Co, ks, wmode, bn_y, bn_st, nullptr, 1.f, bn_part, &fused, true, stream)) return rc;
+  *route = fused ? 1 : 0;
+  const int nblk = fused ? wsl_conv2d_stat_blocks(N, H, W, dy->C, Co, ks) : 0;
+  if (fused == 2)
+    return wsl_bnact_bwd_finish_d_amax(g, g_bs, bn_y, mean, invstd, gamma, beta, dy_out, dgamma, dbeta, N, Co, H, W, bn_part, nblk, 1,
+                                       coef_ws, coef_ws_bytes, dy_amax, stream);
+  if (fused)
+    return wsl_bnact_bwd_finish_amax(g, g_bs, bn_y, mean, invstd, gamma, beta, nullptr, 1.f, dy_out, dgamma, dbeta, N, Co, H, W, bn_part,
+                                     nblk, 1, coef_ws, coef_ws_bytes, dy_amax, stream);
+  return wsl_bnact_bwd_amax(g, g_bs, bn_y, mean, invstd, gamma, beta, nullptr, 1.f, dy_out, dgamma, dbeta, N, Co, H, W, bn_part,
+                            bn_part_bytes, dy_amax, stream);
+}
+
 extern "C" size_t wsl_conv2d_wgrad_ws_bytes(int N, int H, int W, int Ci, int Co, int ks) {
   if (N <= 0 || H <= 0 || W <= 0 || Ci <= 0 || Co <= 0) return 0;
   const WgPlan g = wgrad_plan(N, H, W, Ci, Co), g2 = wgrad_plan(N, H, W, Ci, Co, true), g3 = wgrad_plan(N, H, W, Ci, Co, true, true);
@@ -723,9 +780,21 @@ extern "C" size_t wsl_conv2d_wgrad_ws_bytes(int N, int H, int W, int Ci, int Co,
   return sizeof(float) * (size_t)ns * ((size_t)ks * ks * Co * Ci + Co);
 }
 
+// dy as a virtual tensor: the BatchNorm-backward apply pass of (d, y) with the layer's coefficients, formed by the kernel's loader
+// (wsl_conv2d_wgrad_bnd_partial; `dy` of wgrad_stage1 is d then)
+struct WgBnd {
+  const float* y;
+  int64_t y_bs;
+  const float *mean, *invstd, *gamma, *coef;
+};
+static bool wgrad_small_on() {
+  static const bool on = (WSL_TUNE("WSL_WGRAD_SMALL", 1) != 0);
+  return on;
+}
+
 // first stage of the weight gradient: per-split partial sums into `ws`; *out describes the pending second stage
 static int wgrad_stage1(const WslSrc* a, const WslSrc* b, const float* dy, int64_t dy_bs, float* dw, float* db, int N, int H, int W,
-                        int Co, int ks, void* ws, size_t ws_bytes, void* stream, WslWgradPending* out) {
+                        int Co, int ks, void* ws, size_t ws_bytes, void* stream, WslWgradPending* out, const WgBnd* bnd = nullptr) {
   WSL_REQUIRE(a && dy && dw && ws, "conv2d_wgrad: null argument");
   WSL_REQUIRE(N > 0 && H > 0 && W > 0 && Co > 0, "conv2d_wgrad: bad shape");
   WSL_REQUIRE(ks == 1 || ks == 3, "conv2d_wgrad: kernel size %d not built (1 and 3 are)", ks);
@@ -766,9 +835,14 @@ static int wgrad_stage1(const WslSrc* a, const WslSrc* b, const float* dy, int64
   p.part_db = p.part_dw + (size_t)g.nsplit * KK * Co * Ci;
   p.tiles_x = g.tiles_x, p.tiles_y = g.tiles_y, p.items = g.items, p.nsplit = g.nsplit, p.co_blocks = g.co_blocks;
   // a ci-block beyond the first never writes db and a (co,ci) element outside the tensor is never written: no memset
-  static const bool small_on = (WSL_TUNE("WSL_WGRAD_SMALL", 1) != 0);
-  const int small_kind = (v2 && small_on) ? wgrad_small_kind(p.in.a, &p.in.b, H, W, Co, ks) : 0;
-  if (small_kind) {   // first convolution / 4-class classifier: one narrow operand (wsl_conv4.hip)
+  const int small_kind = (v2 && wgrad_small_on()) ? wgrad_small_kind(p.in.a, &p.in.b, H, W, Co, ks) : 0;
+  if (bnd) {          // first convolution with the virtual dy: the same plan, splits and partials as the raw-dy form below
+    WSL_REQUIRE(small_kind == 1 && !(reinterpret_cast<uintptr_t>(bnd->y) & 15) && !(bnd->y_bs & 3),
+                "conv2d_wgrad_bnd: not a layer wsl_conv2d_wgrad_bnd_ok() accepts");
+    if (int rc = wgrad_small_launch_bnd(p.in.a, dy, dy_bs, bnd->y, bnd->y_bs, bnd->mean, bnd->invstd, bnd->gamma, bnd->coef, p.part_dw,
+                                        p.part_db, N, H, W, g.nsplit, stream))
+      return rc;
+  } else if (small_kind) {   // first convolution / 4-class classifier: one narrow operand (wsl_conv4.hip)
     if (int rc = wgrad_small_launch(small_kind, p.in.a, dy, dy_bs, p.part_dw, p.part_db, N, H, W, g.nsplit, stream)) return rc;
   } else if (v2) {
     if (int rc = wgrad2_launch(p.in.a, &p.in.b, dy, dy_bs, p.part_dw, p.part_db, N, H, W, Co, ks, g.th, g.tw, g.cb, g.ib,
@@ -787,6 +861,24 @@ extern "C" int wsl_conv2d_wgrad_partial(const WslSrc* a, const WslSrc* b, const 
                                         void* stream) {
   WSL_REQUIRE(pending, "conv2d_wgrad_partial: null pending record");
   return wgrad_stage1(a, b, dy, dy_bs, dw, db, N, H, W, Co, ks, ws, ws_bytes, stream, pending);
+}
+
+extern "C" int wsl_conv2d_wgrad_bnd_ok(const WslSrc* a, const WslSrc* b, const float* d, int64_t d_bs, const float* y, int64_t y_bs,
+                                       int H, int W, int Co, int ks) {
+  if (!a || !a->x || !d || !y || H <= 0 || W <= 0 || !wgrad_small_on()) return 0;
+  const WslSrc bb = (b && b->C > 0) ? *b : WslSrc{};
+  if (!wgrad2_eligible(*a, &bb, d, d_bs, W) || wgrad_small_kind(*a, &bb, H, W, Co, ks) != 1) return 0;
+  return d_bs >= (int64_t)Co * H * W && y_bs >= (int64_t)Co * H * W && !(reinterpret_cast<uintptr_t>(y) & 15) && !(y_bs & 3) ? 1 : 0;
+}
+
+extern "C" int wsl_conv2d_wgrad_bnd_partial(const WslSrc* a, const float* d, int64_t d_bs, const float* y, int64_t y_bs,
+                                            const float* mean, const float* invstd, const float* gamma, const float* coef, float* dw,
+                                            float* db, int N, int H, int W, int Co, int ks, void* ws, size_t ws_bytes,
+                                            WslWgradPending* pending, void* stream) {
+  WSL_REQUIRE(pending && y && mean && invstd && gamma && coef, "conv2d_wgrad_bnd_partial: null argument");
+  WSL_REQUIRE(y_bs >= (int64_t)Co * H * W, "conv2d_wgrad_bnd_partial: y batch stride too small");
+  const WgBnd bnd{y, y_bs, mean, invstd, gamma, coef};
+  return wgrad_stage1(a, nullptr, d, d_bs, dw, db, N, H, W, Co, ks, ws, ws_bytes, stream, pending, &bnd);
 }
 
 namespace wsl {

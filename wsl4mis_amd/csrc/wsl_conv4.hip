@@ -23,6 +23,16 @@ struct WgSmallP {
   float* part_db;
   int N, H, W, tiles_x, tiles_y, items, nsplit;
 };
+// virtual-dy form (BND): `a` holds d, the gradient in front of the BatchNorm output; the operand dy is formed from d and the BatchNorm's
+// raw input y while the tile is staged.  (Its own argument struct: the raw-dy instantiations keep their kernel arguments and their code.)
+struct WgSmallBndP : WgSmallP {
+  const float* y = nullptr;   // [N,16,H,W]
+  int64_t y_bs = 0;
+  const float* bn_mean = nullptr;
+  const float* bn_invstd = nullptr;
+  const float* bn_gamma = nullptr;
+  const float* bn_coef = nullptr;   // [16][2] (c1, c2) of wsl_bnact_bwd_coef
+};
 
 template <int CBN>
 struct WgSmallCfg {
@@ -36,12 +46,16 @@ struct WgSmallCfg {
   static constexpr int RED_FLOATS = 4 * 64 * (NT + 1) * 4;
   static constexpr int MAIN_FLOATS = A_FLOATS + B_FLOATS > RED_FLOATS ? A_FLOATS + B_FLOATS : RED_FLOATS;
   static constexpr size_t SMEM = sizeof(float) * (MAIN_FLOATS + 32);
+  static constexpr size_t SMEM_BND = SMEM + sizeof(float) * 5 * 16;   // + [5][16] mean | invstd | sc | c1 | c2
   static_assert(16 % GD == 0 && (4 * CBN) / 16 == (5 * CBN - 1) / 16, "staging shape / centre columns in one tile");
 };
 
 // SGN = +1: B is read at p + tap (first convolution: A = dy, B = x);  -1: at p - tap (classifier: A = activations, B = dy)
-template <int CBN, int SGN>
-__global__ __launch_bounds__(256, 2) void wgrad_small_kernel(WgSmallP p) {
+// BND: the 16-channel operand dy is VIRTUAL -- the loader fetches d and y at the same offsets and forms dy = sc * (d - c1 - xhat * c2)
+// element by element before the LDS store (bn_bwd_dy(): the arithmetic of bnact_bwd_apply4_kernel's d form, the same bits), so the
+// BatchNorm-backward apply pass of a layer without a data gradient never writes dy to memory and nobody reads it back.
+template <int CBN, int SGN, bool BND = false>
+__global__ __launch_bounds__(256, 2) void wgrad_small_kernel(std::conditional_t<BND, WgSmallBndP, WgSmallP> p) {
   using C = WgSmallCfg<CBN>;
   WSL_DYN_SMEM(smem);
   float* a_t = reinterpret_cast<float*>(smem);
@@ -55,6 +69,14 @@ __global__ __launch_bounds__(256, 2) void wgrad_small_kernel(WgSmallP p) {
   const int H = p.H, W = p.W, HW = H * W;
   const bool has_scale = p.a_scale != nullptr;
   if (tid < 16) tab[tid] = has_scale ? make_float2(p.a_scale[tid], p.a_shift[tid]) : make_float2(1.f, 0.f);
+  float* tabd = a_t + C::MAIN_FLOATS + 32;   // (BND) [5][16]
+  if constexpr (BND) {
+    if (tid < 16) {
+      const float invstd = p.bn_invstd[tid];
+      tabd[tid] = p.bn_mean[tid], tabd[16 + tid] = invstd, tabd[32 + tid] = p.bn_gamma[tid] * invstd;
+      tabd[48 + tid] = p.bn_coef[2 * tid], tabd[64 + tid] = p.bn_coef[2 * tid + 1];
+    }
+  }
 
   // fixed staging positions
   const int gd = tid / C::PD, pd = tid - gd * C::PD;
@@ -87,6 +109,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_small_kernel(WgSmallP p) {
   }
   const int st_tx = step % p.tiles_x, st_ty = (step / p.tiles_x) % p.tiles_y, st_n = step / (p.tiles_x * p.tiles_y);
   float4 pra[C::ND], prb[C::NB];
+  float4 pry[BND ? C::ND : 1];
   bool prok[C::NB];
   auto issue = [&]() __attribute__((always_inline)) {
     const int n = nx_n, y0 = nx_ty * C::TH, x0 = nx_tx * C::TW;
@@ -100,6 +123,11 @@ __global__ __launch_bounds__(256, 2) void wgrad_small_kernel(WgSmallP p) {
     const float* ab = p.a + n * p.a_bs + y0 * W + x0;
 #pragma unroll
     for (int i = 0; i < C::ND; ++i) pra[i] = *reinterpret_cast<const float4*>(ab + (int64_t)i * C::GD * HW + taoff);
+    if constexpr (BND) {
+      const float* yb = p.y + n * p.y_bs + y0 * W + x0;
+#pragma unroll
+      for (int i = 0; i < C::ND; ++i) pry[i] = *reinterpret_cast<const float4*>(yb + (int64_t)i * C::GD * HW + taoff);
+    }
     const float* bb = p.b + n * p.b_bs;
 #pragma unroll
     for (int i = 0; i < C::NB; ++i) {
@@ -113,7 +141,14 @@ __global__ __launch_bounds__(256, 2) void wgrad_small_kernel(WgSmallP p) {
 #pragma unroll
     for (int i = 0; i < C::ND; ++i) {
       wsl_v2f lo = {pra[i].x, pra[i].y}, hi = {pra[i].z, pra[i].w};
-      if (has_scale) {
+      if constexpr (BND) {
+        const int ch = gd + i * C::GD;
+        const float mean = tabd[ch], invstd = tabd[16 + ch], sc = tabd[32 + ch], c1 = tabd[48 + ch], c2 = tabd[64 + ch];
+        lo[0] = bn_bwd_dy(lo[0], bn_bwd_xhat(pry[i].x, mean, invstd), sc, c1, c2);
+        lo[1] = bn_bwd_dy(lo[1], bn_bwd_xhat(pry[i].y, mean, invstd), sc, c1, c2);
+        hi[0] = bn_bwd_dy(hi[0], bn_bwd_xhat(pry[i].z, mean, invstd), sc, c1, c2);
+        hi[1] = bn_bwd_dy(hi[1], bn_bwd_xhat(pry[i].w, mean, invstd), sc, c1, c2);
+      } else if (has_scale) {
         const float2 t = tab[gd + i * C::GD];
         xform_bn_leaky(lo, hi, t.x, t.y);
       }
@@ -209,18 +244,19 @@ __global__ __launch_bounds__(256, 2) void wgrad_small_kernel(WgSmallP p) {
   }
 }
 
-template <int CBN, int SGN>
-static int launch_wgrad_small(WgSmallP& p, void* stream) {
+template <int CBN, int SGN, bool BND = false>
+static int launch_wgrad_small(std::conditional_t<BND, WgSmallBndP, WgSmallP>& p, void* stream) {
   using C = WgSmallCfg<CBN>;
-  auto kern = wgrad_small_kernel<CBN, SGN>;
+  auto kern = wgrad_small_kernel<CBN, SGN, BND>;
+  constexpr size_t smem = BND ? C::SMEM_BND : C::SMEM;
   static bool attr_done = false;
   if (!attr_done) {
-    (void)WSL_SET_MAX_DYN_SMEM(kern, C::SMEM);
+    (void)WSL_SET_MAX_DYN_SMEM(kern, smem);
     attr_done = true;
   }
   const double px = (double)p.N * p.H * p.W;
-  void* tok = prof_begin(PF_WGRAD_DIRECT, 2.0 * px * 16 * CBN * 9, 4.0 * px * (16 + CBN), stream);
-  WSL_LAUNCH(kern, dim3(p.nsplit), dim3(kThreads), C::SMEM, stream, p);
+  void* tok = prof_begin(PF_WGRAD_DIRECT, 2.0 * px * 16 * CBN * 9, 4.0 * px * ((BND ? 32 : 16) + CBN), stream);   // BND reads d and y
+  WSL_LAUNCH(kern, dim3(p.nsplit), dim3(kThreads), smem, stream, p);
   prof_end(tok, stream);
   return check_launch("wgrad_small_kernel");
 }
@@ -249,6 +285,20 @@ int wgrad_small_launch(int kind, const WslSrc& a, const float* dy, int64_t dy_bs
   p.a = a.x, p.a_bs = a.bs, p.a_scale = a.scale, p.a_shift = a.shift;
   p.b = dy, p.b_bs = dy_bs;
   return launch_wgrad_small<4, -1>(p, stream);
+}
+
+// kind 1 with a virtual dy = the BatchNorm-backward apply pass of (d, y) with the coefficients coef[16][2] (wsl_bnact_bwd_coef)
+int wgrad_small_launch_bnd(const WslSrc& a, const float* d, int64_t d_bs, const float* y, int64_t y_bs, const float* mean,
+                           const float* invstd, const float* gamma, const float* coef, float* part_dw, float* part_db, int N, int H,
+                           int W, int nsplit, void* stream) {
+  WgSmallBndP p;
+  p.part_dw = part_dw, p.part_db = part_db;
+  p.N = N, p.H = H, p.W = W, p.tiles_x = W / 64, p.tiles_y = H / 8;
+  p.items = N * p.tiles_x * p.tiles_y, p.nsplit = nsplit;
+  p.a = d, p.a_bs = d_bs, p.a_scale = nullptr, p.a_shift = nullptr;
+  p.b = a.x, p.b_bs = a.bs;
+  p.y = y, p.y_bs = y_bs, p.bn_mean = mean, p.bn_invstd = invstd, p.bn_gamma = gamma, p.bn_coef = coef;
+  return launch_wgrad_small<1, 1, true>(p, stream);
 }
 
 
@@ -435,6 +485,18 @@ struct NkP {
   int slots;
   BnBwdEpi bn;
 };
+// The classifier's data gradient in TWO passes of the same staging and MFMA body (PASS template argument of conv_nk16_kernel), with
+// the BatchNorm-backward finalize between them: g = the 16-channel full-resolution gradient is never written to memory.
+//   PASS 1 (statistics): today's kernel without the stores of g -- same tile walk, statistics slots and epilogue: the same partials
+//   PASS 2 (apply):      recomputes g (9 MFMAs per 16 px x 16 ch: the matrix pipe is 0.22 busy in this kernel) and its epilogue is
+//                        bnact_bwd_apply4_kernel's arithmetic on the accumulators: reads y where bn_bwd_acc4 reads it, stores dy
+//                        where PASS 0 stores g
+// (0.25 + 1) + (0.25 + 1 + 1) = 3.5 passes over a 16-channel tensor instead of (0.25 + 1 + 1) + (1 + 1 + 1) = 5.25.
+struct NkApplyP : NkP {   // (its own argument struct: the other instantiations keep their kernel arguments and their code)
+  const float* gamma = nullptr;
+  const float* beta = nullptr;
+  const float* coef = nullptr;   // [16][2] (c1, c2) of wsl_bnact_bwd_coef
+};
 
 template <int CI, int TH_ = 8, int TW_ = 64>
 struct NkCfg {
@@ -451,8 +513,8 @@ struct NkCfg {
 constexpr int kNk16MinW = 2;   // waves per SIMD the register allocator leaves room for.  Round 3 had 3: a 168-register cap that put 56 (CI = 4) /
                                // 12 (CI = 1) values into scratch; measured in round 4 (profiles/r4_minw_ab.log): classifier data gradient
                                // 134 -> 97 us with 2, first convolution 79 -> 78 us
-template <int CI, int TH = 8, int TW = 64, bool NHWC = false>
-__global__ __launch_bounds__(256, kNk16MinW) void conv_nk16_kernel(NkP p) {
+template <int CI, int TH = 8, int TW = 64, bool NHWC = false, int PASS = 0>
+__global__ __launch_bounds__(256, kNk16MinW) void conv_nk16_kernel(std::conditional_t<PASS == 2, NkApplyP, NkP> p) {
   using C = NkCfg<CI, TH, TW>;
   WSL_DYN_SMEM(smem);
   float* in_t = reinterpret_cast<float*>(smem);
@@ -526,7 +588,28 @@ __global__ __launch_bounds__(256, kNk16MinW) void conv_nk16_kernel(NkP p) {
     }
     // (staging the result through LDS so that every store instruction writes four 256-byte row segments instead of sixteen
     //  64-byte pieces was measured SLOWER: 92.5 vs 75.8 us forward, 132.9 vs 115.7 data gradient)
-    if constexpr (NHWC) {
+    if constexpr (PASS == 2) {   // apply pass: dy from the accumulators (bn_dz4()'s d and xhat, bn_bwd_dy()), stored where PASS 0 stores g
+      const float mean = p.bn.st[c16], invstd = p.bn.st[16 + c16];
+      const float sc = p.gamma[c16] * invstd, sh = fmaf(-mean, sc, p.beta[c16]);   // (bnact_bwd_apply4_kernel's coefficients)
+      const float c1 = p.coef[2 * c16], c2 = p.coef[2 * c16 + 1];
+      const float* yin = p.bn.y + ((int64_t)n * 16 + c16) * HW + (int64_t)y0 * W + x0 + 4 * k4;
+      float* yb = p.y + n * p.y_bs + (int64_t)c16 * HW + (int64_t)y0 * W + x0 + 4 * k4;
+#pragma unroll
+      for (int sg = 0; sg < 8; ++sg) {
+        const int off = ((8 * wave + sg) / C::SEGW) * W + 16 * ((8 * wave + sg) % C::SEGW);
+        const float4 yv = *reinterpret_cast<const float4*>(yin + off);
+        const float y4[4] = {yv.x, yv.y, yv.z, yv.w};
+        float v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const float z = fmaf(y4[k], sc, sh);
+          const float d = z > 0.f ? acc[sg][k] : WSL_LEAKY_SLOPE * acc[sg][k];
+          v[k] = bn_bwd_dy(d, bn_bwd_xhat(y4[k], mean, invstd), sc, c1, c2);
+        }
+        *reinterpret_cast<float4*>(yb + off) = make_float4(v[0], v[1], v[2], v[3]);
+      }
+    } else if constexpr (PASS == 1) {   // statistics pass: g stays in the accumulators
+    } else if constexpr (NHWC) {
       float* yb = p.y + n * p.y_bs + ((int64_t)y0 * W + x0 + 4 * k4) * 16 + c16;
 #pragma unroll
       for (int sg = 0; sg < 8; ++sg)
@@ -541,7 +624,7 @@ __global__ __launch_bounds__(256, kNk16MinW) void conv_nk16_kernel(NkP p) {
           make_float4(acc[sg][0], acc[sg][1], acc[sg][2], acc[sg][3]);
     }
 
-    if (p.bn.part) {   // data gradient: BatchNorm-backward statistics of the layer that consumes it
+    if (PASS != 2 && p.bn.part) {   // data gradient: BatchNorm-backward statistics of the layer that consumes it
       const float mean = p.bn.st[c16], invstd = p.bn.st[16 + c16], sc = p.bn.st[32 + c16], sh = p.bn.st[48 + c16];
       const int64_t base = ((int64_t)n * 16 + c16) * HW + (int64_t)y0 * W + x0 + 4 * k4;
       BnBwdAcc ba;
@@ -552,7 +635,7 @@ __global__ __launch_bounds__(256, kNk16MinW) void conv_nk16_kernel(NkP p) {
       float s1[1], s2[1];
       bn_bwd_fold(ba, s1[0], s2[0]);
       bn_bwd_store<1, 16>(p.bn, s1, s2, red, 0, 16, item, p.items);
-    } else if (p.stat_part) {   // forward: per-tile (sum, M2) per channel for the BatchNorm that follows
+    } else if (PASS == 0 && p.stat_part) {   // forward: per-tile (sum, M2) per channel for the BatchNorm that follows
       constexpr float cnt = (float)(C::TH * C::TW);
       float* red1 = red;
       float* red2 = red + 64;
@@ -638,6 +721,51 @@ int conv_nk16_launch(const WslSrc& a, const float* wp, const float* bias, float*
   if (wide && W % 128 == 0) return a.C == 4 ? launch_nk16<4, 4, 128>(p, dgrad, stream) : launch_nk16<1, 4, 128>(p, dgrad, stream);
 #endif
   return a.C == 4 ? launch_nk16<4, 8, 64>(p, dgrad, stream) : launch_nk16<1, 8, 64>(p, dgrad, stream);
+}
+
+// The classifier's data gradient (4 -> 16) without its 16-channel result in memory: PASS 1 leaves the BatchNorm-backward partials in
+// bn.part, the caller finalizes them into coef (wsl_bnact_bwd_coef), PASS 2 writes dy.  Both passes: the tiles, workgroups and MFMA
+// sequence of conv_nk16_launch's data-gradient launch.  Booked under PF_CONV_DGRAD with their own bytes; the algorithmic flops are the
+// statistics pass', the apply pass issues them a second time.
+template <int PASS>
+static int launch_nk16_pass(std::conditional_t<PASS == 2, NkApplyP, NkP>& p, void* stream) {
+  using C = NkCfg<4, 8, 64>;
+  auto kern = conv_nk16_kernel<4, 8, 64, false, PASS>;
+  static bool attr_done = false;
+  if (!attr_done) {
+    (void)WSL_SET_MAX_DYN_SMEM(kern, C::SMEM);
+    attr_done = true;
+  }
+  int wgs = kNk16MinW * device_cu_count();
+  if (wgs > p.items) wgs = p.items;
+  const double px = (double)p.N * p.H * p.W, flops = 2.0 * px * 4 * 16 * 9;
+  // statistics: reads dy_in (4 channels) and y (16); apply: reads them again and writes dy (16)
+  void* tok = PASS == 1 ? prof_begin(PF_CONV_DGRAD, flops, 4.0 * px * (4 + 16), stream)
+                        : prof_begin(PF_CONV_DGRAD, 0.0, 4.0 * px * (4 + 16 + 16), stream, flops);
+  WSL_LAUNCH(kern, dim3(wgs), dim3(kThreads), C::SMEM, stream, p);
+  prof_end(tok, stream);
+  return check_launch(PASS == 1 ? "conv_nk16_kernel(statistics pass)" : "conv_nk16_kernel(apply pass)");
+}
+
+static void nk16_fill(NkP& p, const WslSrc& a, const float* wp, int N, int H, int W, const BnBwdEpi& bn) {
+  p.x = a.x, p.x_bs = a.bs, p.wp = wp, p.bias = nullptr, p.y = nullptr, p.y_bs = (int64_t)16 * H * W;
+  p.N = N, p.H = H, p.W = W, p.tiles_x = W / 64, p.tiles_y = H / 8, p.items = N * p.tiles_x * p.tiles_y;
+  p.stat_part = nullptr, p.stat_cnt = nullptr, p.slots = 1;
+  p.bn = bn;
+}
+
+int conv_nk16_stats_launch(const WslSrc& a, const float* wp, int N, int H, int W, const BnBwdEpi& bn, void* stream) {
+  NkP p;
+  nk16_fill(p, a, wp, N, H, W, bn);
+  return launch_nk16_pass<1>(p, stream);
+}
+
+int conv_nk16_apply_launch(const WslSrc& a, const float* wp, int N, int H, int W, const BnBwdEpi& bn, const float* gamma,
+                           const float* beta, const float* coef, float* dy, void* stream) {
+  NkApplyP p;
+  nk16_fill(p, a, wp, N, H, W, bn);
+  p.y = dy, p.gamma = gamma, p.beta = beta, p.coef = coef;
+  return launch_nk16_pass<2>(p, stream);
 }
 
 // ---- machine probes (EXPERIMENTS build only; tools/mfma_ceiling.py, tools/probe_lds_dma.py, tools/probe_mfma4.py)

@@ -294,6 +294,8 @@ struct GStats {
   int nblk = 0;            // 0: none, run the stand-alone reduction pass
   int channel_major = 0;
   int g_is_d = 0;          // the producer wrote d = g * keep * scale * leaky'(z) in place of g (wsl_conv2d_dgrad_bn_d, *fused == 2)
+  int dy_done = 0;         // the producer ran the whole BatchNorm backward as well: the scratch set's tmp_dy holds dy, the parameter
+                           // gradients are written (wsl_conv2d_dgrad_bn_dy: the classifier's data gradient)
 };
 
 // data-gradient convolution of layer `cv` (dy -> g, dense) that also emits the backward statistics of the BatchNorm whose raw
@@ -303,6 +305,7 @@ static int conv_dgrad_bn(const Ctx& c, const ConvRef& cv, const float* dy, float
   const int N = c.P.d.N, Cg = cv.Ci;
   const WslSrc dys = raw_src(dy, cv.Co, (int64_t)cv.Co * H * W);
   const int64_t g_bs = (int64_t)Cg * H * W;
+  gs->dy_done = 0;
   if (dy_amax && sp_takes(c, cv, &dys, nullptr, g, g_bs, H, W, Cg)) {
     int fused = 0;
     WSL_TRY(wsl_sp_conv2d_dgrad_bn(&dys, dy_amax, c.ws + c.P.spd + sp_img_off(cv), sp_wmax(c, cv), g, g_bs, N, H, W, Cg, c.ws + y,
@@ -425,12 +428,27 @@ static int block_bwd(const Ctx& c, const BlockRef& k, const BlkWs& w, const WslS
   float* dy = c.ws + c.S().tmp_dy;
   float* g1 = c.ws + c.S().tmp_g1;
   // BN2 + LeakyReLU (no dropout after the second activation)
-  WSL_TRY(bn_bwd(c, g, g_bs, w.y2, w.st2, k.b2, nullptr, 1.f, dy, H, W, gs));
+  if (!gs.dy_done) WSL_TRY(bn_bwd(c, g, g_bs, w.y2, w.st2, k.b2, nullptr, 1.f, dy, H, W, gs));
   const WslSrc mid = act_src(c, w.y1, w.st1, C, H * W, emask, es, nullptr);
   WSL_TRY(wgrad_layer(c, &mid, nullptr, dy, CHW, c.grads + k.c2.w, c.grads + k.c2.b, H, W, C, 3, sp_dymax(c, k.b2)));
   // data gradient of the second convolution; its epilogue carries the statistics of BN1 + LeakyReLU + Dropout(p)
   GStats g1s;
   WSL_TRY(conv_dgrad_bn(c, k.c2, dy, g1, H, W, w.y1, w.st1, emask, es, &g1s, sp_dymax(c, k.b2)));
+  // A layer without a data gradient (the first convolution) has ONE reader of its dy, the weight gradient: where the producer delivered
+  // d and nothing needs max |dy|, only the finalize half of the BatchNorm backward runs and the weight gradient's loader forms dy from
+  // (d, y1) on the fly -- no apply launch, no 16-channel full-resolution tensor written and read back (the same bits: bn_bwd_dy())
+  if (!dgrad_out && g1s.nblk && g1s.g_is_d && !sp_dymax(c, k.b1) &&
+      wsl_conv2d_wgrad_bnd_ok(a, b, g1, CHW, c.ws + w.y1, CHW, H, W, C, 3)) {
+    const float* s1 = c.ws + w.st1;
+    float* coef = c.ws + c.S().bn_coef;
+    WSL_TRY(wsl_bnact_bwd_coef(c.ws + c.S().bn_ws, g1s.nblk, g1s.channel_major, P.d.N, C, H, W, c.grads + k.b1.gamma,
+                               c.grads + k.b1.beta, coef, c.stream));
+    const size_t need = (wsl_conv2d_wgrad_ws_bytes(P.d.N, H, W, a->C, C, 3) + 255) & ~(size_t)255;
+    return wgrad_push(c.wb, "net", c.ws + c.S().wg_ws, need, [&](void* ws, size_t n, WslWgradPending* q) {
+      return wsl_conv2d_wgrad_bnd_partial(a, g1, CHW, c.ws + w.y1, CHW, s1, s1 + C, c.params + k.b1.gamma, coef, c.grads + k.c1.w,
+                                          c.grads + k.c1.b, P.d.N, H, W, C, 3, ws, n, q, c.stream);
+    });
+  }
   WSL_TRY(bn_bwd(c, g1, CHW, w.y1, w.st1, k.b1, emask, es, dy, H, W, g1s));
   WSL_TRY(wgrad_layer(c, a, b, dy, CHW, c.grads + k.c1.w, c.grads + k.c1.b, H, W, C, 3, sp_dymax(c, k.b1), raw_amax));
   if (dgrad_out) {
@@ -478,8 +496,26 @@ static int decoder_bwd(const Ctx& c, int k, const float* const* cmasks, const fl
   const WslSrc last = act_src(c, P.wdec[k].blk[3].y2, P.wdec[k].blk[3].st2, kFt[0], H0 * W0, nullptr, 1.f, nullptr);
   WSL_TRY(wgrad_layer(c, &last, nullptr, dlogits, (int64_t)oc.Co * H0 * W0, c.grads + oc.w, c.grads + oc.b, H0, W0, oc.Co, 3));
   // data gradient of the classifier = dL/d(output of up4's block): its epilogue carries that block's BN2 statistics
+  // (together with that BatchNorm's whole backward: where the narrow-K kernel takes the launch, g is recomputed by a second pass that
+  //  writes dy instead of being written and read back -- wsl_conv2d_dgrad_bn_dy; everywhere else it issues conv_dgrad_bn's and bn_bwd's
+  //  launches.  The classifier's data gradient never takes the split path: no max |dy| of the logits' gradient exists.)
   GStats gs;
-  WSL_TRY(conv_dgrad_bn(c, oc, dlogits, g, H0, W0, P.wdec[k].blk[3].y2, P.wdec[k].blk[3].st2, nullptr, 1.f, &gs));
+  {
+    const BlkWs& w3 = P.wdec[k].blk[3];
+    const BnRef& b2 = P.dec[k].blk[3].b2;
+    const int Cg = oc.Ci;
+    const WslSrc dys = raw_src(dlogits, oc.Co, (int64_t)oc.Co * H0 * W0);
+    const float* wt = c.params + oc.w;
+    int wmode = 1, route = 0;
+    if (wsl_conv2d_fast_ok(&dys, nullptr, g, (int64_t)Cg * H0 * W0, W0)) {
+      if (wsl_conv2d_wino_ok(N, H0, W0, oc.Co, 0, Cg, oc.ks)) wt = c.ws + P.winod + 2 * oc.w, wmode = 5;
+      else wt = c.ws + P.packd + oc.w, wmode = 3;
+    }
+    WSL_TRY(wsl_conv2d_dgrad_bn_dy(&dys, wt, g, N, H0, W0, Cg, oc.ks, wmode, c.ws + w3.y2, c.ws + w3.st2, c.params + b2.gamma,
+                                   c.params + b2.beta, c.ws + c.S().bn_ws, P.bn_bytes, c.ws + c.S().tmp_dy, c.grads + b2.gamma,
+                                   c.grads + b2.beta, c.ws + c.S().bn_coef, P.bn_coef_bytes, sp_dymax(c, b2), &route, c.stream));
+    gs.dy_done = 1;
+  }
   for (int i = 3; i >= 0; --i) {
     const int l = 3 - i, c1 = kFt[l + 1], c2 = kFt[l];
     const int h = P.H[l + 1], w = P.W[l + 1], H = P.H[l], W = P.W[l];

@@ -410,6 +410,13 @@ __device__ __forceinline__ void bn_bwd_acc4(const BnBwdEpi& e, int64_t idx, floa
 }
 __device__ __forceinline__ void bn_bwd_fold(const BnBwdAcc& a, float& s1, float& s2) { s1 = a.s1[0] + a.s1[1], s2 = a.s2[0] + a.s2[1]; }
 
+// One element of the BatchNorm-backward apply pass: dy = sc * (d - c1 - xhat * c2), d = the gradient in front of the BatchNorm output,
+// xhat = (y - mean) * invstd, (c1, c2) = the layer's coefficients (mean of d, mean of d * xhat).  ONE definition for the apply kernels
+// (wsl_bn.hip) and for the kernels that form dy on the fly instead of reading it (wgrad_small_kernel's virtual-dy loader), so every
+// copy is the same expression and contracts the same way: the same bits wherever dy is formed.
+__device__ __forceinline__ float bn_bwd_xhat(float y, float mean, float invstd) { return (y - mean) * invstd; }
+__device__ __forceinline__ float bn_bwd_dy(float d, float xh, float sc, float c1, float c2) { return sc * (d - c1 - xh * c2); }
+
 // merge the per-lane sums of a 4-wave workgroup whose lanes (l & 15) own channel column col = j * 16 + (l & 15): lane groups
 // (l >> 4), then waves (through `red`, >= 8 * CO_T floats), then one store per channel into part[C][nb][2]
 // (LDS_ONLY: the barrier publishes `red` without waiting for the caller's global stores and prefetches -- WSL_LDS_BARRIER)
