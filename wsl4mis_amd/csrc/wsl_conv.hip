@@ -161,24 +161,9 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(ConvP p) {
     }
   }
   if (p.stat_part) {  // uniform branch
-    float* red1 = in_t;
-    float* red2 = in_t + 4 * CO_T;
     const int vh = (H - y0 < TH) ? H - y0 : TH, vw = (W - x0 < TW) ? W - x0 : TW;
-    const float cnt = (float)(vh * vw);
-#pragma unroll
-    for (int j = 0; j < C::NT; ++j) {
-      float s = bsum[j];
-      s += __shfl_xor(s, 16);
-      s += __shfl_xor(s, 32);
-      if (lane < 16) red1[wave * CO_T + j * 16 + lane] = s;
-    }
-    __syncthreads();
-    float m2[C::NT];
-#pragma unroll
-    for (int j = 0; j < C::NT; ++j) {
-      const int col = j * 16 + (lane & 15);
-      const int co = co0 + col;
-      const float mean_b = (red1[col] + red1[CO_T + col] + red1[2 * CO_T + col] + red1[3 * CO_T + col]) / cnt;
+    auto sqdev = [=](int j, float mean_b) __attribute__((always_inline)) {
+      const int co = co0 + j * 16 + (lane & 15);
       float q = 0.f;
 #pragma unroll
       for (int i = 0; i < C::MT; ++i) {
@@ -193,26 +178,10 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(ConvP p) {
             }
         }
       }
-      q += __shfl_xor(q, 16);
-      q += __shfl_xor(q, 32);
-      m2[j] = q;
-      if (lane < 16) red2[wave * CO_T + j * 16 + lane] = q;
-    }
-    __syncthreads();
-    if (wave == 0 && lane < 16) {
-#pragma unroll
-      for (int j = 0; j < C::NT; ++j) {
-        const int col = j * 16 + lane, co = co0 + col;
-        if (co < p.Co) {
-          const int64_t nsl = (int64_t)gridDim.x * p.slots;                                   // [Co][slots][2]
-          float* dst = p.stat_part + ((int64_t)co * nsl + (int64_t)blockIdx.x * p.slots) * 2;   // slot 0 of this tile's slots
-          dst[0] = red1[col] + red1[CO_T + col] + red1[2 * CO_T + col] + red1[3 * CO_T + col];
-          dst[1] = red2[col] + red2[CO_T + col] + red2[2 * CO_T + col] + red2[3 * CO_T + col];
-        }
-      }
-      if (lane < p.slots && blockIdx.y == 0) p.stat_cnt[blockIdx.x * p.slots + lane] = lane == 0 ? cnt : 0.f;
-    }
-    (void)m2;
+      return q;
+    };
+    bn_stat_store<C::NT, CO_T>(bsum, (float)(vh * vw), sqdev, in_t, co0, p.Co, (int)blockIdx.x, (int)gridDim.x, p.slots, p.stat_part,
+                               p.stat_cnt, blockIdx.y == 0);
   }
 }
 

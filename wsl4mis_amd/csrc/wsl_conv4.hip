@@ -636,35 +636,21 @@ __global__ __launch_bounds__(256, kNk16MinW) void conv_nk16_kernel(std::conditio
       bn_bwd_fold(ba, s1[0], s2[0]);
       bn_bwd_store<1, 16>(p.bn, s1, s2, red, 0, 16, item, p.items);
     } else if (PASS == 0 && p.stat_part) {   // forward: per-tile (sum, M2) per channel for the BatchNorm that follows
-      constexpr float cnt = (float)(C::TH * C::TW);
-      float* red1 = red;
-      float* red2 = red + 64;
-      float bs = 0.f;
+      float bsum[1] = {0.f};
 #pragma unroll
-      for (int sg = 0; sg < 8; ++sg) bs += (acc[sg][0] + acc[sg][1]) + (acc[sg][2] + acc[sg][3]);
-      bs += __shfl_xor(bs, 16);
-      bs += __shfl_xor(bs, 32);
-      if (lane < 16) red1[wave * 16 + lane] = bs;
-      __syncthreads();
-      const float mean_b = (red1[c16] + red1[16 + c16] + red1[32 + c16] + red1[48 + c16]) / cnt;
-      float q = 0.f;
+      for (int sg = 0; sg < 8; ++sg) bsum[0] += (acc[sg][0] + acc[sg][1]) + (acc[sg][2] + acc[sg][3]);
+      auto sqdev = [=](int, float mean_b) __attribute__((always_inline)) {
+        float q = 0.f;
 #pragma unroll
-      for (int sg = 0; sg < 8; ++sg)
+        for (int sg = 0; sg < 8; ++sg)
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float d = acc[sg][e] - mean_b;
-          q = fmaf(d, d, q);
-        }
-      q += __shfl_xor(q, 16);
-      q += __shfl_xor(q, 32);
-      if (lane < 16) red2[wave * 16 + lane] = q;
-      __syncthreads();
-      if (wave == 0 && lane < 16) {
-        float* dst = p.stat_part + ((int64_t)lane * ((int64_t)p.items * p.slots) + (int64_t)item * p.slots) * 2;   // [Co][slots][2]
-        dst[0] = red1[lane] + red1[16 + lane] + red1[32 + lane] + red1[48 + lane];
-        dst[1] = red2[lane] + red2[16 + lane] + red2[32 + lane] + red2[48 + lane];
-        if (lane < p.slots) p.stat_cnt[item * p.slots + lane] = lane == 0 ? cnt : 0.f;
-      }
+          for (int e = 0; e < 4; ++e) {
+            const float d = acc[sg][e] - mean_b;
+            q = fmaf(d, d, q);
+          }
+        return q;
+      };
+      bn_stat_store<1, 16>(bsum, (float)(C::TH * C::TW), sqdev, red, 0, 16, item, p.items, p.slots, p.stat_part, p.stat_cnt, true);
     }
     __syncthreads();   // the tile and the scratch are free for the next item
   }

@@ -218,23 +218,7 @@ __device__ __forceinline__ void wino2_epilogue(const WinoP& p, v4f (&acc)[16][C:
     return;
   }
   if (p.stat_part) {
-    float* red1 = in_t;
-    float* red2 = in_t + 4 * CO_T;
-    constexpr float cnt = (float)(TH * TW);
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-      float s = bsum[j];
-      s += __shfl_xor(s, 16);
-      s += __shfl_xor(s, 32);
-      if (lane < 16) red1[wave * CO_T + j * 16 + lane] = s;
-    }
-    // (LDS-only barriers: __syncthreads() would also wait -- vmcnt(0) -- until the 32 KB of output stores issued above are acknowledged,
-    //  two microseconds in which a full-resolution workgroup has nothing else to do; only the LDS scratch is shared here)
-    WSL_LDS_BARRIER();
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-      const int col = j * 16 + (lane & 15);
-      const float mean_b = (red1[col] + red1[CO_T + col] + red1[2 * CO_T + col] + red1[3 * CO_T + col]) / cnt;
+    auto sqdev = [=](int j, float mean_b) __attribute__((always_inline)) {
       float q = 0.f;
 #pragma unroll
       for (int m = 0; m < MTW; ++m)
@@ -243,21 +227,12 @@ __device__ __forceinline__ void wino2_epilogue(const WinoP& p, v4f (&acc)[16][C:
           const float d = o[m * NT + j][e] - mean_b;
           q = fmaf(d, d, q);
         }
-      q += __shfl_xor(q, 16);
-      q += __shfl_xor(q, 32);
-      if (lane < 16) red2[wave * CO_T + j * 16 + lane] = q;
-    }
-    WSL_LDS_BARRIER();
-    if (wave == 0 && lane < 16) {
-#pragma unroll
-      for (int j = 0; j < NT; ++j) {
-        const int col = j * 16 + lane, co = co0 + col;
-        float* dst = p.stat_part + ((int64_t)co * ((int64_t)nb * p.slots) + (int64_t)tile_id * p.slots) * 2;   // [Co][slots][2]
-        dst[0] = red1[col] + red1[CO_T + col] + red1[2 * CO_T + col] + red1[3 * CO_T + col];
-        dst[1] = red2[col] + red2[CO_T + col] + red2[2 * CO_T + col] + red2[3 * CO_T + col];
-      }
-      if (lane < p.slots && cby == 0) p.stat_cnt[tile_id * p.slots + lane] = lane == 0 ? cnt : 0.f;
-    }
+      return q;
+    };
+    // (LDS-only barriers: __syncthreads() would also wait -- vmcnt(0) -- until the 32 KB of output stores issued above are acknowledged,
+    //  two microseconds in which a full-resolution workgroup has nothing else to do; only the LDS scratch is shared here)
+    bn_stat_store<NT, CO_T, true>(bsum, (float)(TH * TW), sqdev, in_t, co0, co0 + CO_T, tile_id, nb, p.slots, p.stat_part, p.stat_cnt,
+                                  cby == 0);
   }
 }
 

@@ -716,21 +716,7 @@ __global__ __launch_bounds__(256, (ConvSpCfg<TH, TW, CO_T>::MINW)) void conv_sp_
       }
       if constexpr (EPI == 2) bn_bwd_store<C::NT, CO_T, true>(p.bn, s1, s2, red, co0, Co, t, nb);
       if constexpr (EPI == 1) {
-        float* red1 = red;
-        float* red2 = red + 4 * CO_T;
-        constexpr float cnt = (float)(TH * TW);
-#pragma unroll
-        for (int j = 0; j < C::NT; ++j) {
-          float s = bsum[j];
-          s += __shfl_xor(s, 16);
-          s += __shfl_xor(s, 32);
-          if (lane < 16) red1[wave * CO_T + j * 16 + lane] = s;
-        }
-        WSL_LDS_BARRIER();
-#pragma unroll
-        for (int j = 0; j < C::NT; ++j) {
-          const int col = j * 16 + (lane & 15);
-          const float mean_b = (red1[col] + red1[CO_T + col] + red1[2 * CO_T + col] + red1[3 * CO_T + col]) / cnt;
+        auto sqdev = [=](int j, float mean_b) __attribute__((always_inline)) {
           float q = 0.f;
 #pragma unroll
           for (int i = 0; i < C::MT; ++i)
@@ -739,21 +725,10 @@ __global__ __launch_bounds__(256, (ConvSpCfg<TH, TW, CO_T>::MINW)) void conv_sp_
               const float d = acc[i][j][r] - mean_b;
               q = fmaf(d, d, q);
             }
-          q += __shfl_xor(q, 16);
-          q += __shfl_xor(q, 32);
-          if (lane < 16) red2[wave * CO_T + j * 16 + lane] = q;
-        }
-        WSL_LDS_BARRIER();
-        if (wave == 0 && lane < 16) {
-#pragma unroll
-          for (int j = 0; j < C::NT; ++j) {
-            const int col = j * 16 + lane, co = co0 + col;
-            float* dst = p.stat_part + ((int64_t)co * nb + t) * 2;   // [Co][nblk][2]
-            dst[0] = red1[col] + red1[CO_T + col] + red1[2 * CO_T + col] + red1[3 * CO_T + col];
-            dst[1] = red2[col] + red2[CO_T + col] + red2[2 * CO_T + col] + red2[3 * CO_T + col];
-          }
-          if (lane == 0 && blockIdx.y == 0) p.stat_cnt[t] = cnt;
-        }
+          return q;
+        };
+        // [Co][nblk][2]: one slot per tile
+        bn_stat_store<C::NT, CO_T, true>(bsum, (float)(TH * TW), sqdev, red, co0, co0 + CO_T, t, nb, 1, p.stat_part, p.stat_cnt, blockIdx.y == 0);
       }
     }
   }

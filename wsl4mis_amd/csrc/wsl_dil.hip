@@ -194,8 +194,6 @@ __global__ __launch_bounds__(256) void dil_conv_kernel(DilP p) {
     }
   }
   if (p.stat_part) {  // uniform branch
-    float* red1 = in_t;
-    float* red2 = in_t + 4 * CO_T;
     int vh = 0;   // rows of this tile inside the image: rows ph + d*(r0 + i) < H
     if (ph < H) {
       const int rows_ph = (H - ph + d - 1) / d;
@@ -204,21 +202,9 @@ __global__ __launch_bounds__(256) void dil_conv_kernel(DilP p) {
     }
     const int vw = (W - x0 < TW) ? W - x0 : TW;
     const float cnt = (float)(vh * vw);
-    __syncthreads();   // (red1 / red2 alias the staging tile: every wave is past its last read)
-#pragma unroll
-    for (int j = 0; j < C::NT; ++j) {
-      float s = bsum[j];
-      s += __shfl_xor(s, 16);
-      s += __shfl_xor(s, 32);
-      if (lane < 16) red1[wave * CO_T + j * 16 + lane] = s;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < C::NT; ++j) {
-      const int col = j * 16 + (lane & 15);
-      const int co = co0 + col;
-      const float sum_b = red1[col] + red1[CO_T + col] + red1[2 * CO_T + col] + red1[3 * CO_T + col];
-      const float mean_b = cnt > 0.f ? sum_b / cnt : 0.f;
+    auto sqdev = [=](int j, float mean_q) __attribute__((always_inline)) {
+      const int co = co0 + j * 16 + (lane & 15);
+      const float mean_b = cnt > 0.f ? mean_q : 0.f;   // a tile past the last row of its phase has no valid pixel: sum / cnt is 0 / 0 there
       float q = 0.f;
 #pragma unroll
       for (int i = 0; i < C::MT; ++i) {
@@ -233,23 +219,11 @@ __global__ __launch_bounds__(256) void dil_conv_kernel(DilP p) {
             }
         }
       }
-      q += __shfl_xor(q, 16);
-      q += __shfl_xor(q, 32);
-      if (lane < 16) red2[wave * CO_T + j * 16 + lane] = q;
-    }
-    __syncthreads();
-    if (wave == 0 && lane < 16) {
-#pragma unroll
-      for (int j = 0; j < C::NT; ++j) {
-        const int col = j * 16 + lane, co = co0 + col;
-        if (co < p.Co) {
-          float* dst = p.stat_part + ((int64_t)co * gridDim.x + blockIdx.x) * 2;   // [Co][nblk][2]
-          dst[0] = red1[col] + red1[CO_T + col] + red1[2 * CO_T + col] + red1[3 * CO_T + col];
-          dst[1] = red2[col] + red2[CO_T + col] + red2[2 * CO_T + col] + red2[3 * CO_T + col];
-        }
-      }
-      if (lane == 0 && blockIdx.y == 0) p.stat_cnt[blockIdx.x] = cnt;
-    }
+      return q;
+    };
+    __syncthreads();   // (the helper's scratch aliases the staging tile: every wave is past its last read)
+    // [Co][nblk][2]: one slot per tile
+    bn_stat_store<C::NT, CO_T>(bsum, cnt, sqdev, in_t, co0, p.Co, (int)blockIdx.x, (int)gridDim.x, 1, p.stat_part, p.stat_cnt, blockIdx.y == 0);
   }
 }
 

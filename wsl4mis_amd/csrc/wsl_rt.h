@@ -420,6 +420,9 @@ __device__ __forceinline__ float bn_bwd_dy(float d, float xh, float sc, float c1
 // merge the per-lane sums of a 4-wave workgroup whose lanes (l & 15) own channel column col = j * 16 + (l & 15): lane groups
 // (l >> 4), then waves (through `red`, >= 8 * CO_T floats), then one store per channel into part[C][nb][2]
 // (LDS_ONLY: the barrier publishes `red` without waiting for the caller's global stores and prefetches -- WSL_LDS_BARRIER)
+// The forward sibling is bn_stat_store() below: same lane / wave / `red` layout.  One deliberate difference, the order of the wave
+// merge: pairwise (w0 + w1) + (w2 + w3) here, left to right in bn_stat_store.  Changing either order changes the bits of every training
+// step, so the two reductions are NOT to be merged.
 template <int NT, int CO_T, bool LDS_ONLY = false>
 __device__ __forceinline__ void bn_bwd_store(const BnBwdEpi& e, float (&s1)[NT], float (&s2)[NT], float* red, int co0, int Co,
                                              int tile_id, int nb) {
@@ -445,6 +448,62 @@ __device__ __forceinline__ void bn_bwd_store(const BnBwdEpi& e, float (&s1)[NT],
         dst[1] = (r2[col] + r2[CO_T + col]) + (r2[2 * CO_T + col] + r2[3 * CO_T + col]);
       }
     }
+  }
+}
+
+// BatchNorm FORWARD statistics fused into the epilogue of the conv kernel that produces y: per tile and channel (sum, M2 about the
+// tile's own mean) into stat_part[Co][ntiles * slots][2] at the tile's slot 0, and the tile's element count into
+// stat_cnt[ntiles * slots] (0 in its other slots) -- what wsl_bn_stats_finalize merges.  Same lane / wave / `red` layout (>= 8 * CO_T
+// floats) as bn_bwd_store() above, its backward sibling, with ONE deliberate difference: the four waves are summed left to right,
+// w0 + w1 + w2 + w3, not pairwise.  Do not merge the two reductions: changing either order changes the bits of every training step.
+//   bsum[j]           the lane's sum over its valid elements of channel column j * 16 + (l & 15)
+//   cnt               valid elements of the tile per channel (a compile-time constant at the full-tile call sites: it folds)
+//   sqdev(j, mean_b)  the call site's loop over its own accumulator registers: the lane's sum of (v - mean_b)^2 over the same
+//                     elements, q = fmaf(d, d, q) in the site's element order.  The sites capture BY VALUE ([=]): the accumulators then
+//                     stay plain values through inlining; captured by reference the closure holds their address until after the first
+//                     simplification passes and the generic kernels came out with another register allocation (88 instead of 68 / 72)
+//   Co                channels of the layer; a site whose channel blocks are full by eligibility passes co0 + CO_T (the guard folds)
+//   slots             statistics slots per tile (wsl_conv2d_stat_blocks); the [Co][nblk][2] layouts are slots = 1
+//   first_cblk        this workgroup writes the tile's count (one channel block per tile does)
+// (LDS_ONLY: as bn_bwd_store)
+template <int NT, int CO_T, bool LDS_ONLY = false, class SqDev>
+__device__ __forceinline__ void bn_stat_store(const float (&bsum)[NT], float cnt, SqDev&& sqdev, float* red, int co0, int Co, int tile,
+                                              int ntiles, int slots, float* stat_part, float* stat_cnt, bool first_cblk) {
+  // (the wave index in a scalar register, as conv_sp_kernel's copy had it: the row of `red` and the final `wave == 0` are scalar work)
+  const int lane = threadIdx.x & 63, wave = WSL_WAVE_UNIFORM((int)(threadIdx.x >> 6));
+  float* red1 = red;
+  float* red2 = red + 4 * CO_T;
+#pragma unroll
+  for (int j = 0; j < NT; ++j) {
+    float s = bsum[j];
+    s += __shfl_xor(s, 16);
+    s += __shfl_xor(s, 32);
+    if (lane < 16) red1[wave * CO_T + j * 16 + lane] = s;
+  }
+  if constexpr (LDS_ONLY) WSL_LDS_BARRIER();
+  else __syncthreads();
+#pragma unroll
+  for (int j = 0; j < NT; ++j) {
+    const int col = j * 16 + (lane & 15);
+    const float mean_b = (red1[col] + red1[CO_T + col] + red1[2 * CO_T + col] + red1[3 * CO_T + col]) / cnt;
+    float q = sqdev(j, mean_b);
+    q += __shfl_xor(q, 16);
+    q += __shfl_xor(q, 32);
+    if (lane < 16) red2[wave * CO_T + j * 16 + lane] = q;
+  }
+  if constexpr (LDS_ONLY) WSL_LDS_BARRIER();
+  else __syncthreads();
+  if (wave == 0 && lane < 16) {
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+      const int col = j * 16 + lane, co = co0 + col;
+      if (co < Co) {
+        float* dst = stat_part + ((int64_t)co * ((int64_t)ntiles * slots) + (int64_t)tile * slots) * 2;   // slot 0 of this tile's slots
+        dst[0] = red1[col] + red1[CO_T + col] + red1[2 * CO_T + col] + red1[3 * CO_T + col];
+        dst[1] = red2[col] + red2[CO_T + col] + red2[2 * CO_T + col] + red2[3 * CO_T + col];
+      }
+    }
+    if (lane < slots && first_cblk) stat_cnt[tile * slots + lane] = lane == 0 ? cnt : 0.f;
   }
 }
 
