@@ -83,6 +83,9 @@ def main(argv=None):
                     "supervised runs), 'labeled' / 'unlabeled' = the subsets of dataset_semi.py")
     ap.add_argument("--snapshot_path", default=None, help="write the reference's checkpoints here (state_dict .pth files)")
     ap.add_argument("--save_every", type=int, default=3000)
+    ap.add_argument("--val_path", default="host", choices=["host", "device"], help="validation: 'host' = scipy zoom and numpy masks per "
+                    "slice (the reference's loop); 'device' = val_2D.VolumeValidator (zoom, argmax and Dice counts in HIP kernels, the "
+                    "volumes uploaded once; equal label maps and Dice)")
     ap.add_argument("--no_hd95", action="store_true", help="validation: Dice only (the model-selection metric), skip HD95")
     ap.add_argument("--log_every", type=int, default=20)
     ap.add_argument("--quiet", action="store_true", help="no per-iteration lines (validation lines stay)")
@@ -139,6 +142,12 @@ def main(argv=None):
     torch.manual_seed(args.seed + 1000 * rank)          # dropout masks differ per rank; beta is shared (python RNG)
     order = np.random.RandomState(args.seed + rank)
     it, best, history = 0, 0.0, []
+    validator = None
+    if args.val_path == "device" and len(val):
+        # The fold's volumes, uploaded once and kept across the passes.  Every rank keeps ALL of them although it validates only its share
+        # (run(indices=range(rank, len(val), world)) below): the indices then are the dataset's own on every rank, and the cost is small --
+        # a fold of ACDC is about 110 MB of fp32 images + uint8 labels on the device, read from files the dataset caches anyway.
+        validator = val_2D.VolumeValidator([val[i] for i in range(len(val))], args.num_classes, args.patch_size)
     log = [] if (args.curve_json and rank == 0) else None
     import time
     t_start = time.time()
@@ -214,10 +223,13 @@ def main(argv=None):
                     dist.broadcast(eng.model._nbt, src=0)
                 volume_fn = val_2D.test_single_volume_cct if args.model == "unet_cct" else val_2D.test_single_volume
                 acc = np.zeros(2 * (args.num_classes - 1) + 1)
-                for i in range(rank, len(val), world):
-                    v = val[i]
-                    m = np.array(volume_fn(v["image"], v["label"], eng.model, args.num_classes, args.patch_size,
-                                           with_hd95=not args.no_hd95), dtype=np.float64)
+                if validator is not None:
+                    per_volume = validator.run(eng.model, first_output=args.model == "unet_cct", with_hd95=not args.no_hd95,
+                                               indices=range(rank, len(val), world))
+                else:
+                    per_volume = [np.array(volume_fn(val[i]["image"], val[i]["label"], eng.model, args.num_classes, args.patch_size,
+                                                     with_hd95=not args.no_hd95), dtype=np.float64) for i in range(rank, len(val), world)]
+                for m in per_volume:
                     acc += np.concatenate([m[:, 0], m[:, 1], [1.0]])
                 if world > 1:
                     t = torch.from_numpy(acc).cuda()

@@ -547,6 +547,41 @@ int wsl_nearest_dist2(const int64_t* a_zyx, int na, const int64_t* b_zyx, int nb
 int wsl_nearest_dist2_sp(const int64_t* a_zyx, int na, const int64_t* b_zyx, int nb, double sz, double sy, double sx, double* out,
                          void* stream);
 
+/* On-device validation (ref: code/val_2D.py:18-50 test_single_volume, :90-124 test_single_volume_cct): the two per-slice
+ * scipy.ndimage.zoom(order=0) calls around the eval forward and the argmax between them.  Conventions of the data-path entries: no
+ * allocation, no synchronisation, descriptor arrays on the HOST (copied into the launch, 64 slices of any mix of sizes per launch),
+ * every argument checked before the first launch (WSL_EINVAL: nothing was launched, nothing written).
+ *
+ * wsl_val_zoom_in: out[k] = scipy.ndimage.zoom(slices[k].img, (Ho / h, Wo / w), order=0) with the default mode='constant', cval=0,
+ * bit for bit: nearest input sample floor(o * (in - 1) / (out - 1) + 0.5) in double without contraction, and 0.0f -- scipy's fill,
+ * NOT the edge pixel -- in the last row / column of the pairs (in, out) whose last coordinate exceeds in - 1 by an ulp
+ * (256 -> 216, 256 -> 105, 26 -> 12, ...; wsl_augment_batch clamps there, needs a label and takes 32 samples per launch). */
+typedef struct {
+  const float* img;   /* [h, w] native slice (device pointer) */
+  int h, w;
+} WslValSrc;
+int wsl_val_zoom_in(const WslValSrc* slices, int n, float* out /* [n,1,Ho,Wo] */, int Ho, int Wo, void* stream);
+/* wsl_val_labelmap: for native pixel (y, x) of slice k, with (Y, X) the sample of the [Hn, Wn] logits that the same rule picks
+ * (network size -> native):  pred[y, x] = the FIRST index of the maximum of z[k, :, Y, X] (np.argmax / torch.argmax on finite logits;
+ * NaN is outside the contract), or 0 where the coordinate is outside (scipy's fill) -- exactly
+ *     zoom(argmax(z[k]).astype(uint8), (h / Hn, w / Wn), order=0)
+ * without ever writing an [n, Hn, Wn] label map: only the sampled logits are read.  pred may be ANY byte address (a slice inside a
+ * [D, h, w] uint8 volume with odd h * w): 32-bit stores are used only for aligned words that lie inside [pred, pred + h * w), single
+ * bytes at the ends.  With label != NULL and counts != NULL, for every class c < C
+ *     counts[group][c][0] += |pred == c|,  [1] += |label == c|,  [2] += |pred == c & label == c|        (label values >= C count nowhere)
+ * over the slice: what Dice needs per volume (group = the volume).  Integer sums: lane -> wave -> workgroup, then one 64-bit integer
+ * atomic add per counter and workgroup -- independent of the order, hence bit-reproducible; no workspace.  counts is ADDED to (the
+ * caller zeroes it).  Refused: C outside 1 .. 8, n <= 0, null z, a null pred, h or w < 1, a group outside [0, n_groups) while counts
+ * is given. */
+typedef struct {
+  uint8_t* pred;          /* [h, w] out */
+  const uint8_t* label;   /* [h, w] or NULL (no counts for this slice) */
+  int h, w;
+  int group;              /* row of counts */
+} WslValDst;
+int wsl_val_labelmap(const float* z /* [n,C,Hn,Wn] logits */, const WslValDst* slices, int n, int C, int Hn, int Wn,
+                     int64_t* counts /* [n_groups, C, 3], ADDED to; may be NULL */, int n_groups, void* stream);
+
 /* Noisy copies of a batch for the mean-teacher / USTM teachers (ref: train_mean_teacher_2D.py:147-149, ..._ustm_2D.py:125-135):
  * out[r*n + i] = x[i] + d,  r < reps, with d = noise[r*n + i] when `noise` is given (parity tests replay the reference's draw)
  * or clamp(N(0,1) * sigma, -clip, clip) drawn by the library (Philox4x32-10 + Box-Muller, reproducible per seed). */

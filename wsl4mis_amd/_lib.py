@@ -76,6 +76,14 @@ class WslAugSampleS2l(C.Structure):
                 ("m01", C.c_double), ("m10", C.c_double), ("m11", C.c_double), ("off0", C.c_double), ("off1", C.c_double)]
 
 
+class WslValSrc(C.Structure):
+    _fields_ = [("img", c_fp), ("h", C.c_int32), ("w", C.c_int32)]
+
+
+class WslValDst(C.Structure):
+    _fields_ = [("pred", c_fp), ("label", c_fp), ("h", C.c_int32), ("w", C.c_int32), ("group", C.c_int32)]
+
+
 i32, i64, f32, f64, sz = C.c_int, C.c_int64, C.c_float, C.c_double, C.c_size_t
 PS, PD, PE = C.POINTER(WslSrc), C.POINTER(WslNetDesc), C.POINTER(WslNetEntry)
 PP = C.POINTER(c_fp)
@@ -178,6 +186,8 @@ _PROTOS = {
     "wsl_s2l_head_fwd_bwd": (i32, [c_fp, c_fp, c_fp, i32, f32, f32, f32, c_fp, c_fp, c_fp, i32, i32, i32, c_fp, sz, c_fp]),
     "wsl_s2l_ensemble_update": (i32, [c_fp, C.POINTER(WslS2lSlot), i32, i32, i32, i32, f64, c_fp]),
     "wsl_augment_batch_s2l": (i32, [C.POINTER(WslAugSampleS2l), i32, i32, c_fp, c_fp, c_fp, c_fp, i32, i32, c_fp]),
+    "wsl_val_zoom_in": (i32, [C.POINTER(WslValSrc), i32, c_fp, i32, i32, c_fp]),
+    "wsl_val_labelmap": (i32, [c_fp, C.POINTER(WslValDst), i32, i32, i32, i32, c_fp, i32, c_fp]),
     "wsl_random_walker_ws_bytes": (sz, [i32, i32, i32, i32]),
     "wsl_random_walker": (i32, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, i32, i32, i32, i32, f32, f32, i32, c_fp, sz, c_fp]),
     "wsl_noisy_copy": (i32, [c_fp, c_fp, c_fp, i64, i32, f32, f32, C.c_uint64, c_fp]),

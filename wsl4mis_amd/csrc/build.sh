@@ -18,7 +18,7 @@ set -euo pipefail
 here="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 root="$(cd "$here/../.." && pwd)"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
-srcs=(wsl_api wsl_conv wsl_conv2 wsl_conv4 wsl_conv5 wsl_convsp wsl_bn wsl_convt wsl_loss wsl_optim wsl_net wsl_data wsl_dil wsl_pnet wsl_s2l wsl_rw wsl_semi wsl_dan)
+srcs=(wsl_api wsl_conv wsl_conv2 wsl_conv4 wsl_conv5 wsl_convsp wsl_bn wsl_convt wsl_loss wsl_optim wsl_net wsl_data wsl_dil wsl_pnet wsl_s2l wsl_rw wsl_semi wsl_dan wsl_val)
 export LC_ALL=C
 SRC_SHA="$(cat $(ls "$here"/*.hip "$here"/*.h | sort) "$root/include/wsl_hip.h" | sha256sum | cut -d' ' -f1)"
 HDR_SHA="$(cat $(ls "$here"/*.h | sort) "$root/include/wsl_hip.h" | sha256sum | cut -d' ' -f1)"   # every private header: none can be forgotten

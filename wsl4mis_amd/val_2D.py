@@ -6,7 +6,9 @@ host-side glue.  medpy is not available offline: Dice is computed here, and HD95
 distances; 95th percentile with numpy's linear rule) with the two heavy pieces on the device (`wsl_surface_u8`,
 `wsl_nearest_dist2`: exact integer squared distances) and `torch.nonzero` / `torch.sort` as plumbing.  With a
 `voxelspacing` (the offline test stage, test_2D_fully.py: distances in millimetres) the nearest-surface search is
-`wsl_nearest_dist2_sp` in fp64; `asd_percase` is medpy's directed `asd`."""
+`wsl_nearest_dist2_sp` in fp64; `asd_percase` is medpy's directed `asd`.
+Opt-in, the slice loop itself runs on the device (`predict_volume_device`, `VolumeValidator`, `on_device=True`: both zooms, the argmax
+and the Dice counts in csrc/wsl_val.hip), with equal label maps and Dice; the host loop stays the default."""
 import numpy as np
 import torch
 from scipy.ndimage import zoom
@@ -156,7 +158,133 @@ def _squeeze(v):
     return a[0] if a.ndim == 4 else a            # DataLoader batch dimension of the reference (val_2D.py:19-20)
 
 
-def test_single_volume(image, label, net, classes, patch_size=(256, 256), with_hd95=True):
+# ------------------------------------------------------------------------------------------------ the same on the device
+# wsl_val_zoom_in -> eval forward -> wsl_val_labelmap (csrc/wsl_val.hip): both zooms are scipy's order-0 rule to the last pixel, the
+# argmax is the first maximum, the Dice counts are integers -- label maps and Dice EQUAL the host path's; nothing crosses PCIe per
+# slice.  The host path above stays as it is (and stays the default of every caller).
+
+def _device_volume(vol, dtype, what):
+    """a [D,h,w] volume (numpy or a host tensor: uploaded; a tensor already on the device: used in place when it has the dtype) as a
+    contiguous device tensor"""
+    if isinstance(vol, torch.Tensor):
+        if vol.device != rt.device() and vol.device.type != "cpu":
+            raise rt._lib.WslError(f"{what} lives on {vol.device}, expected {rt.device()}")
+        t = vol.detach().to(dtype).to(rt.device()).contiguous()
+    else:
+        t = torch.from_numpy(np.ascontiguousarray(np.asarray(vol), dtype={torch.float32: np.float32, torch.uint8: np.uint8}[dtype]))
+        t = t.to(rt.device())
+    if t.dim() == 4 and t.shape[0] == 1:
+        t = t[0]                                  # DataLoader batch dimension of the reference (val_2D.py:19-20)
+    if t.dim() != 3:
+        raise NotImplementedError(f"{what}: 2-D slices of a [D,H,W] volume are the built path, got {tuple(t.shape)}")
+    return t
+
+
+def _zoomed_logits(net, first_output, patch_size, jobs):
+    """`jobs` = [(image volume, pred volume, label volume or None, slice index, group)]: their slices zoomed to the patch size and sent
+    through ONE forward -> logits [n, C, Ho, Wo]"""
+    n, (Ho, Wo) = len(jobs), patch_size
+    src = (rt._lib.WslValSrc * n)()
+    for k, (img, _, _, d, _) in enumerate(jobs):
+        h, w = img.shape[1:]
+        src[k].img, src[k].h, src[k].w = img.data_ptr() + 4 * d * h * w, h, w
+    x = torch.empty((n, 1, Ho, Wo), dtype=torch.float32, device=rt.device())
+    rt.call("wsl_val_zoom_in", src, n, rt.ptr(x), Ho, Wo, rt.stream())
+    with torch.no_grad():
+        out = net(x)
+        if first_output and isinstance(out, (tuple, list)):
+            out = out[0]                          # val_2D.py:104: only the main branch is evaluated
+    return rt.f32c(out, "logits")
+
+
+def _label_maps(z, jobs, counts=None):
+    """the label bytes of the jobs' slices from their logits, into the pred volumes; counts [groups, C, 3] int64: the Dice counts, added"""
+    n = len(jobs)
+    dst = (rt._lib.WslValDst * n)()
+    for k, (img, pred, lab, d, group) in enumerate(jobs):
+        h, w = img.shape[1:]
+        dst[k].pred, dst[k].h, dst[k].w, dst[k].group = pred.data_ptr() + d * h * w, h, w, group
+        dst[k].label = None if lab is None else lab.data_ptr() + d * h * w
+    rt.call("wsl_val_labelmap", rt.ptr(z), dst, n, z.shape[1], z.shape[2], z.shape[3], rt.ptr(counts),
+            0 if counts is None else counts.shape[0], rt.stream())
+
+
+def predict_volume_device(image, net, patch_size, first_output, slices_per_forward=16):
+    """`_predict_volume` without the host: -> uint8 device tensor [D,h,w], equal to it byte for byte at the same slices_per_forward.
+    `image`: numpy (uploaded once) or a tensor already on the device (used in place).  Like `_predict_volume` it puts `net` into eval
+    mode and LEAVES it there: a training loop calls `net.train()` afterwards."""
+    img = _device_volume(image, torch.float32, "image")
+    pred = torch.empty(tuple(img.shape), dtype=torch.uint8, device=rt.device())
+    net.eval()
+    for i0 in range(0, img.shape[0], slices_per_forward):
+        jobs = [(img, pred, None, d, 0) for d in range(i0, min(i0 + slices_per_forward, img.shape[0]))]
+        _label_maps(_zoomed_logits(net, first_output, tuple(patch_size), jobs), jobs)
+    return pred
+
+
+class VolumeValidator:
+    """The validation set of a fold kept on the device across validation passes: `volumes` is an iterable of
+    {"image": [D,h,w], "label": [D,h,w]} (what BaseDataSets(split="val") yields), uploaded once as fp32 / uint8.  run() packs the
+    slices of all selected volumes into forwards of `slices_per_forward`, across volume boundaries (the eval forward is per-sample),
+    and reads the Dice counts back ONCE per pass."""
+
+    def __init__(self, volumes, classes, patch_size=(256, 256), slices_per_forward=64):
+        self.classes, self.patch_size, self.slices_per_forward = int(classes), tuple(int(p) for p in patch_size), int(slices_per_forward)
+        self.images = [_device_volume(v["image"], torch.float32, "image") for v in volumes]
+        self.labels = [_device_volume(v["label"], torch.uint8, "label") for v in volumes]
+        for a, b in zip(self.images, self.labels):
+            if a.shape != b.shape:
+                raise ValueError(f"image {tuple(a.shape)} and label {tuple(b.shape)} differ in shape")
+        self._pred = {}
+
+    def __len__(self):
+        return len(self.images)
+
+    def run(self, net, first_output=False, with_hd95=True, indices=None):
+        """-> np.float64 [len(indices), classes - 1, 2] of (dice, hd95): `metric_percase` per volume and class 1 .. classes - 1.
+        `indices`: the volumes of this pass (a data-parallel rank takes range(rank, len, world)); default all.
+        Puts `net` into eval mode and LEAVES it there, as the host path does: a training loop calls `net.train()` afterwards."""
+        idx = list(range(len(self.images))) if indices is None else [int(i) for i in indices]
+        res = np.zeros((len(idx), self.classes - 1, 2), dtype=np.float64)
+        self._pred = {}
+        if not idx:
+            return res
+        net.eval()
+        jobs = []
+        for g, i in enumerate(idx):
+            self._pred[i] = torch.empty(tuple(self.images[i].shape), dtype=torch.uint8, device=rt.device())
+            jobs += [(self.images[i], self._pred[i], self.labels[i], d, g) for d in range(self.images[i].shape[0])]
+        counts = None
+        for j0 in range(0, len(jobs), self.slices_per_forward):
+            part = jobs[j0:j0 + self.slices_per_forward]
+            z = _zoomed_logits(net, first_output, self.patch_size, part)
+            if counts is None:                    # (the logits say how many classes the net has)
+                counts = torch.zeros((len(idx), z.shape[1], 3), dtype=torch.int64, device=rt.device())
+            _label_maps(z, part, counts)
+        cnt = counts.cpu().numpy()                # the pass's one read: [volume, class, (|pred|, |gt|, |pred & gt|)]
+        for g, i in enumerate(idx):
+            for c in range(1, self.classes):
+                n_pred, n_gt, inter = (int(v) for v in cnt[g, c]) if c < cnt.shape[1] else (0, 0, 0)
+                if n_pred == 0:
+                    continue                      # metric_percase: (0, 0) when nothing is predicted
+                res[g, c - 1, 0] = 2.0 * inter / (n_pred + n_gt)
+                if with_hd95:                     # (raises medpy's RuntimeError when the ground truth is empty, as the host path)
+                    res[g, c - 1, 1] = hd95_percase(self._pred[i] == c, self.labels[i] == c)
+        return res
+
+    def predictions(self):
+        """{volume index: uint8 device tensor [D,h,w]} of the last pass"""
+        return dict(self._pred)
+
+
+def _metrics_on_device(image, label, net, classes, patch_size, with_hd95, first_output):
+    v = VolumeValidator([{"image": image, "label": label}], classes, patch_size, slices_per_forward=16)
+    return [(float(dice), float(hd95)) for dice, hd95 in v.run(net, first_output=first_output, with_hd95=with_hd95)[0]]
+
+
+def test_single_volume(image, label, net, classes, patch_size=(256, 256), with_hd95=True, on_device=False):
+    if on_device:
+        return _metrics_on_device(image, label, net, classes, patch_size, with_hd95, first_output=False)
     image, label = _squeeze(image), _squeeze(label)
     if image.ndim != 3:
         raise NotImplementedError("2-D slices of a [D,H,W] volume are the built path (the reference's else-branch "
@@ -165,7 +293,9 @@ def test_single_volume(image, label, net, classes, patch_size=(256, 256), with_h
     return [metric_percase(prediction == i, label == i, with_hd95) for i in range(1, classes)]
 
 
-def test_single_volume_cct(image, label, net, classes, patch_size=(256, 256), with_hd95=True):
+def test_single_volume_cct(image, label, net, classes, patch_size=(256, 256), with_hd95=True, on_device=False):
+    if on_device:
+        return _metrics_on_device(image, label, net, classes, patch_size, with_hd95, first_output=True)
     image, label = _squeeze(image), _squeeze(label)
     if image.ndim != 3:
         raise NotImplementedError("2-D slices of a [D,H,W] volume are the built path (val_2D.py:116 unpacks four "
